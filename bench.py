@@ -24,8 +24,17 @@ bytes over the sum of the push's kernels (`path`), and the predicate pass (4.125
 rocprofv3 PMC summary of this same command (profiles/r05/collect.sh, FETCH_SIZE x2 + WRITE_SIZE passes) and is only
 used when its kernel-source hash matches the tree.
 The JSON line ends with `whole_node` and `roofline` (the driver keeps the line's tail).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` needs: it generates the stream, warms up,
+times the K steps and prints the line (with the roofline of those same steps: their HIP-event times cost no run of
+their own).  `--full` adds every measurement that takes runs of its own -- `whole_node`, `cpu_baseline` and `configs`
+(the other BASELINE configs and the streaming sub-lines) -- which are null / empty in a plain line.
+`--dump-outputs DIR` writes what the last timed step delivered (the match records pending in HBM, as a caller of
+sg_device_records sees them) to DIR/<name>.npy: the stream is generated from fixed seeds, so two builds can be
+compared output for output (dump_records).
 """
 import argparse
+import ctypes as ct
 import hashlib
 import json
 import os
@@ -387,7 +396,66 @@ def roofline_of(cfg, n, matches, kern, stage):
     return roof
 
 
-def measure_push(cfg, rank, n, keys, rate, dev, steps, warmup, sync_ranks=False):
+DUMP_BYTES = 48 << 20   # of the 64 MB a dump may take
+DUMP_CHUNK = 1 << 25    # records copied out of the engine's store at a time (2 GB of 64-byte records)
+
+
+def dump_records(h, nfa, out_dir, dev, rank=0, ws=1):
+    """--dump-outputs: the match records the last timed step left pending in HBM (sg_device_records: what a caller of
+    the timed path receives), one .npy per record field.  Every record while they fit DUMP_BYTES, else a fixed sample:
+    the records are cut into equal strata in delivery order and one record is drawn from each with a seeded generator,
+    so the same indices (`sample_index`) are drawn whenever the match count is the same.  `matches` holds the full
+    count.  Integers are written as float64 (event indices, ids and ms timestamps are below 2^53: exact), FLOAT
+    columns as float32, DOUBLE as float64; a null value is written as NaN."""
+    m = h.device_records()
+    torch.cuda.synchronize()
+    words = m.record_bytes // 8
+    dts = N.column_dtypes(nfa)[:m.n_select]
+    k = int(min(m.n, DUMP_BYTES // max(1, ws) // (8 * (6 + len(dts)))))
+    if k < m.n:
+        edges = (np.arange(k + 1, dtype=np.int64) * m.n) // k
+        idx = edges[:-1] + (np.random.default_rng(20240229).random(k) * (edges[1:] - edges[:-1])).astype(np.int64)
+    else:
+        idx = np.arange(k, dtype=np.int64)
+    rows = torch.empty((k, words), dtype=torch.int64, device=dev)
+    ix = torch.from_numpy(idx).to(dev)
+    hip = ct.CDLL("libamdhip64.so")
+    for s0 in range(0, m.n, DUMP_CHUNK):
+        c = min(m.n - s0, DUMP_CHUNK)
+        lo, hi = (int(x) for x in np.searchsorted(idx, [s0, s0 + c]))
+        if lo == hi:
+            continue
+        buf = torch.empty((c, words), dtype=torch.int64, device=dev)
+        rc = hip.hipMemcpy(ct.c_void_p(buf.data_ptr()), ct.c_void_p(m.base + s0 * m.record_bytes),
+                           ct.c_size_t(c * m.record_bytes), 3)   # hipMemcpyDeviceToDevice
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy of the match records failed ({rc})")
+        rows[lo:hi] = buf[ix[lo:hi] - s0]
+        del buf
+    rec = rows.cpu().numpy()
+    del rows, ix
+    half = rec.view(np.int32).reshape(k, 2 * words)
+    vnull = half[:, 6].view(np.uint32)
+    out = {"matches": np.array([m.n], np.float64), "sample_index": idx.astype(np.float64),
+           "trigger": rec[:, 0].view(np.uint64).astype(np.float64), "ts": rec[:, 1].astype(np.float64),
+           "key": half[:, 4].astype(np.float64), "group": half[:, 5].view(np.uint32).astype(np.float64),
+           "vnull": vnull.astype(np.float64)}
+    for j, dt in enumerate(dts):
+        v = np.ascontiguousarray(rec[:, 4 + j])
+        if dt is np.float32:
+            v = np.ascontiguousarray(v.view(np.int32).reshape(k, 2)[:, 0]).view(np.float32).copy()
+        elif dt is np.float64:
+            v = v.view(np.float64).copy()
+        else:
+            v = v.astype(np.float64)
+        v[((vnull >> np.uint32(j)) & np.uint32(1)).astype(bool)] = np.nan
+        out["col%d" % j] = v
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, (name if ws == 1 else "rank%d_%s" % (rank, name)) + ".npy"), a)
+
+
+def measure_push(cfg, rank, n, keys, rate, dev, steps, warmup, sync_ranks=False, dump=None):
     """K timed sg_push steps of one batch resident in HBM (fresh state each step), HIP-event kernel times."""
     g, key, cols = synth_columns(cfg, rank, n, keys, rate, dev)
     torch.cuda.synchronize()
@@ -434,6 +502,8 @@ def measure_push(cfg, rank, n, keys, rate, dev, steps, warmup, sync_ranks=False)
     if sync_ranks:
         elapsed = reduce_max(elapsed)
         barrier()
+    if dump:
+        dump_records(h, nfa, dump, dev, rank, dist_env()[0])
     h.close()
     del g, key, cols
     torch.cuda.empty_cache()
@@ -519,7 +589,7 @@ def config_line(cfg, dev, steps, warmup, cpu):
     return out
 
 
-def c5_stream(rank, ws, dev, steps, warmup, total, push_rows):
+def c5_stream(rank, ws, dev, steps, warmup, total, push_rows, dump=None):
     """BASELINE configs[4] as it is worded: ONE 1B-event, 1M-key C5 stream sharded by key hash across the node's
     ranks (strong scaling: the stream is the same at every N).  Every rank generates the global stream in HBM chunk
     by chunk and keeps the rows of the keys it owns (siddhi_amd/router.py shard_of_torch: mix64(key) mod N, the host
@@ -572,6 +642,8 @@ def c5_stream(rank, ws, dev, steps, warmup, total, push_rows):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     el, all_matches, rows = reduce_max(el), reduce_sum(matches), reduce_sum(n)
+    if dump:   # (records accumulate over a step's pushes until delivered: the whole last step is pending)
+        dump_records(h, nfa, dump, dev, rank, ws)
     h.close()
     del cat, batches
     torch.cuda.empty_cache()
@@ -734,7 +806,18 @@ def main():
                     help="run the whole-node pipeline in a child process (-1: when N > 1, so a fault on the multi-GPU "
                          "exchange path cannot take the headline line with it)")
     ap.add_argument("--node-only", action="store_true", help=argparse.SUPPRESS)   # (the child's mode)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the whole-node pipeline, the CPU baselines, the other "
+                         "configs and the streaming sub-lines (their options above select among them); without it "
+                         "only the headline is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the match records of the last step to DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample when they exceed 48 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full and not args.node_only:
+        args.c5_node_steps, args.no_cpu, args.other_configs, args.stream_configs = 0, True, "", ""
     if args.node_only:
         print(json.dumps({"whole_node": whole_node_block(args, 1, 0, torch.device("cuda", 0))}))
         return
@@ -753,7 +836,8 @@ def main():
     if cfg == "C5":
         # ---- value: the metric's config, inputs resident in HBM: ONE 1B-event, 1M-key stream sharded by key hash
         # over the ranks (strong scaling), pushed in 500M-row batches with carried state
-        head = c5_stream(rank, ws, dev, args.steps, args.warmup, args.c5_events, args.c5_push_rows)
+        head = c5_stream(rank, ws, dev, args.steps, args.warmup, args.c5_events, args.c5_push_rows,
+                         dump=args.dump_outputs)
         value, ms_step = head["value"], head["ms_per_step"]
         roof = head.pop("roofline")
         n, matches = head["events"], head["matches"]
@@ -764,7 +848,8 @@ def main():
         pmc_cfg = "C5"
     else:
         n = args.events or min(n_cfg, 100_000_000)
-        m = measure_push(cfg, rank, n, keys, rate, dev, args.steps, args.warmup, sync_ranks=ws > 1)
+        m = measure_push(cfg, rank, n, keys, rate, dev, args.steps, args.warmup, sync_ranks=ws > 1,
+                         dump=args.dump_outputs)
         ms_step = m["elapsed"] * 1000.0 / args.steps
         value = ws * n * args.steps / m["elapsed"]
         matches = m["matches"]
@@ -826,7 +911,7 @@ def main():
         "metric": "events/sec (whole node) for partitioned pattern query at 1/2/4/8 GPUs; % HBM peak",
         "value": round(value, 1), "unit": "events/s", "n_gpus": ws, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic (SplitMix64 generator, SURVEY.md §8d), inputs resident in HBM; matches "
+        "dtype": "f32", "full": bool(args.full), "data": "synthetic (SplitMix64 generator, SURVEY.md §8d), inputs resident in HBM; matches "
                                "projected in HBM (zero-copy sg_device_records)",
         "config": conf,
         "cpu_baseline": cpu,

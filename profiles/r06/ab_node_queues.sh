@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/abq
 for q in ${QS:-8 16 24}; do
-  SG_NODE_CHILD_QUEUES=$q timeout -k 10 600 python -u bench.py --steps 1 --warmup 0 --no-cpu --other-configs= --stream-configs= \
+  SG_NODE_CHILD_QUEUES=$q timeout -k 10 600 python -u bench.py --full --steps 1 --warmup 0 --no-cpu --other-configs= --stream-configs= \
     --c5-node-steps 1 --node-shards ${SHARDS:-4,8} > gpurun_out/abq/q$q.json 2> gpurun_out/abq/q$q.err || exit 1
   python -c "
 import json

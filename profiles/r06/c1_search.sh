@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_time_regression.py tests/test_walker_paths.py tests/test_full_size.py tests/test_gpu_parity.py \
   -k "unpartitioned or c1 or C1 or long_completion or walker or kat" > $OUT/tests.log 2>&1 || { echo "tests failed"; tail -30 $OUT/tests.log; exit 1; }
 tail -2 $OUT/tests.log
-timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs C1,C2 --stream-configs= \
+timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs C1,C2 --stream-configs= \
   --other-steps 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 python -c "
 import json

@@ -24,7 +24,7 @@ for cfg in "$@"; do
   done
   if [ "$cfg" == "C5" ]; then
     timeout -s KILL 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$d/pmc_node" -o run -- \
-      python3 -u bench.py --config C5 --steps 1 --warmup 0 --no-cpu --other-configs= --stream-configs= --c5-node-steps 1 \
+      python3 -u bench.py --full --config C5 --steps 1 --warmup 0 --no-cpu --other-configs= --stream-configs= --c5-node-steps 1 \
       --node-shards 2 > "$d/pmc_node.log" 2>&1 || { echo "C5 pmc pass with the whole-node stage failed"; tail -5 "$d/pmc_node.log"; exit 1; }
     rm -rf "$d/pmc_node"
   fi

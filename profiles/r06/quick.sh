@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_wide_partition.py tests/test_c5_headline.py "tests/test_time_regression.py" -k "wide or C5 or c5 or headline" \
   > $OUT/tests.log 2>&1 || { echo "tests failed"; tail -40 $OUT/tests.log; exit 1; }
 tail -3 $OUT/tests.log
-timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs C2 --other-steps 2 \
+timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs C2 --other-steps 2 \
   > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
 python -c "
 import json,sys

@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_group_walk.py tests/test_c5_headline.py tests/test_partial_lanes.py -k "group or headline or bounded" \
   > $OUT/tests.log 2>&1 || { echo "tests failed"; tail -30 $OUT/tests.log; exit 1; }
 tail -2 $OUT/tests.log
-timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs= \
+timeout -k 10 400 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --c5-node-steps 0 --other-configs= \
   --stream-configs ${STREAMS:-C3c,C3c+bounded} --other-steps 2 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
 python -c "
 import json
