@@ -491,7 +491,10 @@ static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t
     const size_t bytes = (size_t)(se - sub) * sel.stride;
     char* dst = out + (size_t)(out_base + sub) * sel.stride;
     if ((((uintptr_t)dst) & 15) == 0) {
-      for (size_t x = (size_t)t * 16; x < bytes; x += 256 * 16) *(U4*)(dst + x) = *(const U4*)(stage + x);
+      // (an odd select count makes the stride 8 mod 16: an odd number of records ends on a half word, which a 16-byte
+      // store would carry 8 bytes into the next tile's first record -- another workgroup's, or past the buffer)
+      for (size_t x = (size_t)t * 16; x + 16 <= bytes; x += 256 * 16) *(U4*)(dst + x) = *(const U4*)(stage + x);
+      if ((bytes & 8) && t == 255) *(uint64_t*)(dst + bytes - 8) = *(const uint64_t*)(stage + bytes - 8);
     } else {
       for (size_t x = (size_t)t * 8; x < bytes; x += 256 * 8) *(uint64_t*)(dst + x) = *(const uint64_t*)(stage + x);
     }
