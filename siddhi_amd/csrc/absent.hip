@@ -35,12 +35,7 @@
 
 #include "sg_device.h"
 #include "sg_engine.h"
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+#include "sg_prim.h"
 
 namespace {
 
@@ -776,19 +771,13 @@ void sort_and_kill(SgHandle* h, const AbsArgs& a, uint64_t omin, int bits, const
   uint32_t* sid = (uint32_t*)h->ws.get("abs_sid", 4 * nt, st);
   const K sentinel = (K)(bits >= (int)(8 * sizeof(K)) ? ~(K)0 : ((K)1 << bits) - 1);
   hipLaunchKernelGGL((k_abs_keys<K>), dim3(grid_for(nt)), dim3(256), 0, st, nt, role, vals, omin, sentinel, keys, ids);
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys, ids, sid, (size_t)nt, 0, bits, st));
-  void* tmp = h->ws.get("abs_sort_tmp", tb, st);
-  HIPCHK(rocprim::radix_sort_pairs(tmp, tb, keys, skeys, ids, sid, (size_t)nt, 0, bits, st));
+  sg_radix_sort_pairs(h->ws, st, "abs_sort_tmp", keys, skeys, ids, sid, (size_t)nt, bits);
   uint32_t* nks = nullptr;
   if (!a.fast) {
     uint32_t* rk = (uint32_t*)h->ws.get("abs_rk", 4 * nt, st);
     nks = (uint32_t*)h->ws.get("abs_nks", 4 * nt, st);
     hipLaunchKernelGGL(k_abs_rkill, dim3(grid_for(nt)), dim3(256), 0, st, nt, sid, role, rk);
-    tb = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, tb, rk, nks, (size_t)nt, rocprim::minimum<uint32_t>(), st));
-    tmp = h->ws.get("abs_scan_tmp", tb, st);
-    HIPCHK(rocprim::inclusive_scan(tmp, tb, rk, nks, (size_t)nt, rocprim::minimum<uint32_t>(), st));
+    sg_inclusive_scan(h->ws, st, "abs_scan_tmp", rk, nks, (size_t)nt, rocprim::minimum<uint32_t>());
   }
   if (a.fast && bits < 64)   // below 64 bits the sentinel lies above every value key
     hipLaunchKernelGGL((k_abs_kill_fast<K>), dim3(grid_for(nt)), dim3(256), 0, st, a, skeys, sid, sentinel, ts, c_dl, dead,
@@ -883,13 +872,8 @@ static int64_t run_seq(SgHandle* h, AbsState* as, const AbsArgs& a, const BatchV
     uint32_t* fl = (uint32_t*)h->ws.get("sa_flag", 4 * (np + 1), st);
     uint32_t* fo = (uint32_t*)h->ws.get("sa_foff", 4 * (np + 1), st);
     hipLaunchKernelGGL(k_abs_seq_alive, dim3(grid_for(np + 1)), dim3(256), 0, st, np, s.palive, fl);
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, fl, fo, 0u, (size_t)np + 1, rocprim::plus<uint32_t>(), st));
-    void* tmp = h->ws.get("sa_scan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, fl, fo, 0u, (size_t)np + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t ncar = 0;
-    HIPCHK(hipMemcpyAsync(&ncar, fo + np, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_exclusive_scan(h->ws, st, "sa_scan_tmp", fl, fo, 0u, (size_t)np + 1, rocprim::plus<uint32_t>());
+    uint32_t ncar = sg_read_back(fo + np, st);
     cout.reserve(std::max<int64_t>(ncar, 1), d.n_select);
     if (ncar)
       hipLaunchKernelGGL(k_abs_seq_carry, dim3(grid_for(np)), dim3(256), 0, st, a, o, bv.cols, bv.ts, np, fl, fo, s.psrc,
@@ -1025,14 +1009,9 @@ static int64_t absent_segment(SgHandle* h, const BatchView& bv, int64_t n, bool 
   if (nt > 0)
     hipLaunchKernelGGL(k_abs_decide, dim3(grid_for(nt)), dim3(256), 0, st, a, role, dead, bv.ts, cin.dl, trig, cnt);
   HIPCHK(hipMemsetAsync(cnt + nt, 0, 8, st));
-  size_t tb = 0;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tb, cnt, off, (uint64_t)0, (size_t)nt + 1, rocprim::plus<uint64_t>(), st));
-  void* tmp = h->ws.get("abs_oscan_tmp", tb, st);
-  HIPCHK(rocprim::exclusive_scan(tmp, tb, cnt, off, (uint64_t)0, (size_t)nt + 1, rocprim::plus<uint64_t>(), st));
+  sg_exclusive_scan(h->ws, st, "abs_oscan_tmp", cnt, off, (uint64_t)0, (size_t)nt + 1, rocprim::plus<uint64_t>());
   h->kend();
-  uint64_t tot = 0;
-  HIPCHK(hipMemcpyAsync(&tot, off + nt, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  uint64_t tot = sg_read_back(off + nt, st);
   const int64_t n_emit = (int64_t)(tot & 0xffffffffull), n_carry = (int64_t)(tot >> 32);
   h->mark(3);
   // ---- 6. write
@@ -1058,10 +1037,7 @@ static int64_t absent_segment(SgHandle* h, const BatchView& bv, int64_t n, bool 
     hipLaunchKernelGGL(k_abs_slot_trig, dim3(grid_for(nt)), dim3(256), 0, st, nt, cnt, off, trig, slot_trig);
     uint32_t* head = (uint32_t*)h->ws.get("abs_head", 4 * (n_emit + 1), st);
     hipLaunchKernelGGL(k_abs_heads, dim3(grid_for(n_emit)), dim3(256), 0, st, n_emit, slot_trig, head);
-    size_t tb2 = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, tb2, head, first_slot, (size_t)n_emit, rocprim::maximum<uint32_t>(), st));
-    void* tmp2 = h->ws.get("abs_head_scan_tmp", tb2, st);
-    HIPCHK(rocprim::inclusive_scan(tmp2, tb2, head, first_slot, (size_t)n_emit, rocprim::maximum<uint32_t>(), st));
+    sg_inclusive_scan(h->ws, st, "abs_head_scan_tmp", head, first_slot, (size_t)n_emit, rocprim::maximum<uint32_t>());
   }
   if (nt > 0)
     hipLaunchKernelGGL(k_abs_write, dim3(grid_for(nt)), dim3(256), 0, st, a, o, bv.cols, bv.ts, trig, cnt, off, vals,
@@ -1082,13 +1058,8 @@ static int64_t absent_segment(SgHandle* h, const BatchView& bv, int64_t n, bool 
     uint32_t* qo = (uint32_t*)h->ws.get("abs_qo", 4 * (ne_q + 1), st);
     hipLaunchKernelGGL(k_abs_qcount, dim3(grid_for(ne_q + 1)), dim3(256), 0, st, nq_in, qin.v, n, bv.ts, role, a.nc, kc,
                        a.W, clock1, qm);
-    size_t tq = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tq, qm, qo, 0u, (size_t)ne_q + 1, rocprim::plus<uint32_t>(), st));
-    void* tmpq = h->ws.get("abs_qscan_tmp", tq, st);
-    HIPCHK(rocprim::exclusive_scan(tmpq, tq, qm, qo, 0u, (size_t)ne_q + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t nq1 = 0;
-    HIPCHK(hipMemcpyAsync(&nq1, qo + ne_q, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_exclusive_scan(h->ws, st, "abs_qscan_tmp", qm, qo, 0u, (size_t)ne_q + 1, rocprim::plus<uint32_t>());
+    uint32_t nq1 = sg_read_back(qo + ne_q, st);
     qout.reserve(std::max<int64_t>(nq1, 1));
     hipLaunchKernelGGL(k_abs_qwrite, dim3(grid_for(ne_q)), dim3(256), 0, st, nq_in, qin.v, n, bv.ts, a.W, qm, qo, qout.v);
     HIPCHK(hipGetLastError());

@@ -11,12 +11,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "sg_engine.h"
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+#include "sg_prim.h"
 
 struct sg_handle {
   SgHandle h;
@@ -99,13 +94,8 @@ static void run_select(SgHandle& h) {
     hipLaunchKernelGGL(k_select, grd, blk, 0, st, n, (const char*)h.stage.rec, 32 + 8 * d.n_select, tmp, ostride,
                        h.ddesc, keep);
     HIPCHK(hipGetLastError());
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, keep, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    void* tsc = h.ws.get("having_scan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tsc, tb, keep, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t kept = 0;
-    HIPCHK(hipMemcpyAsync(&kept, pos + n, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_exclusive_scan(h.ws, st, "having_scan_tmp", keep, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>());
+    uint32_t kept = sg_read_back(pos + n, st);
     if (kept) {
       char* out = h.out.reserve(kept, d.n_out, st);
       hipLaunchKernelGGL(k_having_scatter, grd, blk, 0, st, n, (const char*)tmp, keep, pos, ostride,

@@ -24,10 +24,6 @@ void sg_every_next_reset(SgHandle* h) {
 // Snapshot of the closed form's state: the carried rows (per key, the rows still inside `within` of the key's
 // last event -- they rebuild e2's pending list, StreamPreStateProcessor.currentState
 // C/query/input/stream/state/StreamPreStateProcessor.java:352-359) and the null history of the columns.
-static int col_bytes(const sg_nfa_desc& d, int c) {
-  return (d.col_type[c] == SG_T_LONG || d.col_type[c] == SG_T_DOUBLE) ? 8 : 4;
-}
-
 void sg_every_next_snapshot(SgHandle* h, SnapW& w) {
   const sg_nfa_desc& d = h->desc;
   EveryNextState* es = (h->state && h->state_kind == 1) ? (EveryNextState*)h->state : nullptr;
@@ -40,7 +36,7 @@ void sg_every_next_snapshot(SgHandle* h, SnapW& w) {
   w.dev(cs.key, n * 4, h->stream);
   w.dev(cs.flags, n, h->stream);
   for (int c = 0; c < d.n_cols; ++c) {
-    w.dev(cs.col[c], n * col_bytes(d, c), h->stream);
+    w.dev(cs.col[c], n * sg_col_width(d.col_type[c]), h->stream);
     w.dev(cs.nul[c], n, h->stream);
   }
 }
@@ -60,7 +56,7 @@ void sg_every_next_restore(SgHandle* h, SnapR& r) {
   r.dev(cs.key, n * 4, h->stream);
   r.dev(cs.flags, n, h->stream);
   for (int c = 0; c < d.n_cols; ++c) {
-    r.dev(cs.col[c], n * col_bytes(d, c), h->stream);
+    r.dev(cs.col[c], n * sg_col_width(d.col_type[c]), h->stream);
     r.dev(cs.nul[c], n, h->stream);
   }
   cs.n = n;

@@ -1,8 +1,9 @@
 // gwalk.h -- the closed form's group walker: `every A[l] -> B[l' and B.x OP A.x] within T` when the partition has
 // many keys with few rows each (C5: 1M keys, ~500 rows per key per 500M-row push, ~10 rows per `within` window).
-// Included by engine_impl.h; run_group_walk is tried by run_every_next after the partition's group passes.
+// Kernels first, then the host side (gw_plan, run_group_walk); run_every_next (engine_impl.h) tries run_group_walk
+// after the partition's group passes (keypart.h part1_wide).
 //
-// Semantics are those of the tiled walker (engine_impl.h Walker::step, itself StreamPreStateProcessor.isExpired /
+// Semantics are those of the tiled walker (walk.h Walker::step, itself StreamPreStateProcessor.isExpired /
 // processAndReturn, C/query/input/stream/state/StreamPreStateProcessor.java:102-113,292-337, and
 // StreamPostStateProcessor.process, StreamPostStateProcessor.java:53-72): per key, e2's pending list in arrival order,
 // an arriving row first drops the partials older than `within`, then completes every pending partial its compare
@@ -21,10 +22,21 @@
 // arrival order gives each trigger's first output slot, and the projection walks the triggers in arrival order,
 // so the output records are written contiguously and in delivery order.
 //
-// The fast path declines (returns false, nothing changed) when a push needs what only the tiled path has: a key
+// The fast path declines (run_group_walk returns 0, nothing changed) when a push needs what only the tiled path has: a key
 // whose time goes back (the exact HBM-list walker), a pending list longer than the LDS ring, e1 attributes gathered
 // by row, or a select reading anything but the compared values and the carried payload.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+
+#include "keypart.h"
+#include "sg_engine.h"
+#include "sg_prim.h"
+#include "walk.h"
 
 struct GwArgs {
   int64_t n, nc;              // batch rows; carried rows (virtual rows [0, nc))
@@ -502,3 +514,228 @@ static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side of the group walker: whether a query and a push can take it (gw_plan), and one push through it
+// (run_group_walk).
+struct GwPlan {
+  bool ok = false;
+  int cap = 0;
+  GwSel sel;
+};
+// span_ms: time from the push's first to its last batch row (the ring is sized as the tiled walker sizes it)
+template <class T>
+static GwPlan gw_plan(SgHandle* h, const BatchView& bv, int64_t n, int64_t nc, uint32_t kb, const PushPlan& plan,
+                      bool same_col, int64_t span_ms) {
+  const sg_nfa_desc& d = h->desc;
+  GwPlan g;
+  memset(&g.sel, 0, sizeof(g.sel));
+  if (!d.partitioned || !same_col || plan.e1_row || d.n_select > SG_MAX_SELECT) return g;
+  for (int c = 0; c < d.n_cols; ++c)
+    if (bv.cols.nul[c]) return g;
+  for (int s = 0; s < d.n_select; ++s) {
+    const int src = plan.pp.src[s], kind = plan.pp.kind[s];
+    int code = -1;
+    if (kind == 2) code = 4;
+    else if (kind == 0 && src == 0) code = 0;
+    else if (kind == 1) code = src ? 2 : 1;
+    else if (kind == 3 && src == 1 && plan.pcol >= 0 && plan.pp.col[s] == plan.pcol) code = 3;
+    if (code < 0) return g;
+    g.sel.code[s] = code;
+  }
+  const int64_t win = window_rows(kb, nc + n, d.within, span_ms);
+  // the ring as the tiled walker sizes it (a key whose list outgrows it is walked again on an unbounded list by
+  // k_gw_redo); the LDS chunk shrinks as the ring grows so two workgroups share a CU (launch_gwalk)
+  const char* e = getenv("SG_DEBUG_GW_CAP");   // (test hook)
+  int cap = h->opt.ring_cap > 0 ? h->opt.ring_cap : (e ? atoi(e) : pick_cap(win));
+  if (cap > 32 || cap < 2 || (cap & (cap - 1))) return g;
+  g.cap = cap;
+  g.sel.n_select = d.n_select;
+  g.sel.stride = 32 + 8 * d.n_select;
+  g.sel.vfloat = std::is_same<T, float>::value ? 1 : 0;
+  g.ok = true;
+  return g;
+}
+
+template <class T, int OP, int PT, bool STACK>
+static void launch_gwalk_pt(const GwArgs& ga, uint32_t ng, hipStream_t st) {
+  const size_t lds = sizeof(GwLds<PT>) + (size_t)ga.cap * 256 * (sizeof(T) + 8);
+  HIPCHK(hipFuncSetAttribute((const void*)k_gwalk<T, OP, PT, STACK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_gwalk<T, OP, PT, STACK>), dim3(ng), dim3(256), lds, st, ga);
+  HIPCHK(hipGetLastError());
+}
+template <class T, int OP>
+static void launch_gw_redo(const GwArgs& ga, uint32_t nk, uint32_t* rows, T* hv, int32_t* ht, int32_t* hp, hipStream_t st) {
+  if (ga.stack_mode) hipLaunchKernelGGL((k_gw_redo<T, OP, true>), dim3(nk), dim3(256), 0, st, ga, rows, hv, ht, hp);
+  else hipLaunchKernelGGL((k_gw_redo<T, OP, false>), dim3(nk), dim3(256), 0, st, ga, rows, hv, ht, hp);
+  HIPCHK(hipGetLastError());
+}
+template <class T, int OP>
+static void launch_gwalk(const GwArgs& ga, uint32_t ng, hipStream_t st) {
+  // rows per thread per LDS chunk: the largest that leaves room for two workgroups per CU beside the ring (measured on
+  // C5, profiles/r06/ab_gw.sh: 8 with an 8-entry ring, 6 with 16; with 32 one workgroup per CU whatever the chunk)
+  const char* e = getenv("SG_DEBUG_GW_PT");   // (test hook)
+  const int pt = e ? atoi(e) : (ga.cap <= 8 ? 8 : ga.cap <= 16 ? 6 : 4);
+  if (ga.stack_mode) {
+    if (pt == 4) launch_gwalk_pt<T, OP, 4, true>(ga, ng, st);
+    else if (pt == 12) launch_gwalk_pt<T, OP, 12, true>(ga, ng, st);
+    else if (pt == 10) launch_gwalk_pt<T, OP, 10, true>(ga, ng, st);
+    else if (pt == 6) launch_gwalk_pt<T, OP, 6, true>(ga, ng, st);
+    else launch_gwalk_pt<T, OP, 8, true>(ga, ng, st);
+  } else {
+    launch_gwalk_pt<T, OP, 8, false>(ga, ng, st);
+  }
+}
+
+// the delivered matches of a group-walked push -> output records: per-tile match counts -> tile bases (scan) ->
+// output records per tile (block scan inside the tile)
+static void gw_project(SgHandle* h, const BatchView& bv, int64_t n, const GwArgs& ga, const GwSel& sel, uint32_t total) {
+  const sg_nfa_desc& d = h->desc;
+  hipStream_t st = h->stream;
+  char* out = h->out.reserve(total, d.n_select, st);
+  const int64_t ntile = (n + GW_TILE - 1) / GW_TILE;
+  uint32_t* tcount = (uint32_t*)h->ws.get("gw_tcount", sizeof(uint32_t) * ((size_t)ntile + 1), st);
+  uint32_t* tbase = (uint32_t*)h->ws.get("gw_tbase", sizeof(uint32_t) * ((size_t)ntile + 1), st);
+  h->kbeg("gw_tiles");
+  HIPCHK(hipMemsetAsync(tcount + ntile, 0, sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_gtile_count, dim3((unsigned)((ntile + 7) / 8)), dim3(256), 0, st, n, (const uint64_t*)ga.trig, tcount,
+                     ntile);
+  HIPCHK(hipGetLastError());
+  sg_exclusive_scan(h->ws, st, "gw_tscan_tmp", tcount, tbase, (uint32_t)0, (size_t)ntile + 1, rocprim::plus<uint32_t>());
+  h->kend();
+  uint32_t tsum = 0;
+  HIPCHK(hipMemcpyAsync(&tsum, tbase + ntile, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  h->kbeg("gw_project");
+  const size_t plds = (size_t)GW_PROJ_S * sel.stride;
+  if (plds > 65536)
+    HIPCHK(hipFuncSetAttribute((const void*)k_gscan_project, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+  hipLaunchKernelGGL(k_gscan_project, dim3((unsigned)ntile), dim3(256), plds, st, n, ga.t0, bv.base_index, bv.index,
+                     (const uint64_t*)ga.trig, (const uint64_t*)ga.area, sel, (int64_t)h->out.n, out,
+                     (const uint32_t*)tbase);
+  HIPCHK(hipGetLastError());
+  h->kend();
+  HIPCHK(hipStreamSynchronize(st));
+  if (tsum != total) throw SgError(SG_EINVAL, "internal: group walker match count mismatch");
+  h->out.n += total;
+}
+
+// One push whose partition ran pass 1 in two (more than 65,536 keys) through the group walker.  Returns 1 when it
+// delivered the push, 2 when the push needs wide records (the caller returns false), 0 when it declines.  A declined
+// call has only read o1 / grec / glk / pk_flags and written workspaces of its own (gw_*, and cv_*, which the record
+// pass acquires again): nothing was delivered, and neither h->out, the carry sets nor the push counters changed, so
+// the caller goes on with pass 2 of the partition and the tiled walker.
+template <class T>
+static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t nc, uint32_t kb, const PartPlan& pp,
+                          const uint32_t* o1, const WRec<T, true>* grec, const uint8_t* glk, uint32_t* pk_flags,
+                          const GwPlan& gp, const PushPlan& plan, const Virt& v, const SgCols& cc, int op, int stack_mode,
+                          int val_col_a, EveryNextState* es) {
+  const sg_nfa_desc& d = h->desc;
+  hipStream_t st = h->stream;
+  const int64_t nt = nc + n;
+  const uint32_t ng = (kb + 255) >> 8;
+  // per-key rows -> each key's first row in the group domain (its match-area region starts at 3x that)
+  uint32_t* kcnt = (uint32_t*)h->ws.get("gw_kcnt", sizeof(uint32_t) * ((size_t)kb + 1), st);
+  uint32_t* kbase = (uint32_t*)h->ws.get("gw_kbase", sizeof(uint32_t) * ((size_t)kb + 1), st);
+  h->kbeg("gw_count");
+  HIPCHK(hipMemsetAsync(kcnt, 0, sizeof(uint32_t) * ((size_t)kb + 1), st));
+  hipLaunchKernelGGL(k_gw_count, dim3(ng), dim3(256), 0, st, o1, pp.ns1, kb, glk, kcnt);
+  HIPCHK(hipGetLastError());
+  sg_exclusive_scan(h->ws, st, "gw_kscan_tmp", kcnt, kbase, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
+  h->kend();
+  uint32_t pkf = 0;
+  int64_t t0 = 0;   // narrow records' time origin: the push's first virtual row
+  HIPCHK(hipMemcpyAsync(&pkf, pk_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&t0, nc ? v.c_ts : v.ts, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const PackRange pr = pack_range(pkf);
+  if (pr == PACK_TS_RANGE) return 2;
+  if (pr == PACK_PAY_RANGE) return 0;   // a payload wider than 32 bits: the tiled path gathers e1 by row
+  h->mark(2);
+
+  GwArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.n = n;
+  ga.nc = nc;
+  ga.within = d.within;
+  ga.t0 = t0;
+  ga.K = kb;
+  ga.ns1 = pp.ns1;
+  ga.stack_mode = stack_mode;
+  ga.cap = gp.cap;
+  ga.chunk = 4096;
+  ga.carry_out = h->opt.no_carry ? 0 : 1;
+  ga.pzero = v.pfloat;
+  ga.o1 = o1;
+  ga.grec = (const PtU4*)grec;
+  ga.glk = glk;
+  ga.kbase = kbase;
+  ga.trig = (uint64_t*)h->ws.get("gw_trig", sizeof(uint64_t) * ((size_t)n + 1), st);
+  ga.area = (uint64_t*)h->ws.get("gw_area", sizeof(uint64_t) * 3 * (size_t)std::max<int64_t>(nt, 1), st);
+  uint32_t* gflags = (uint32_t*)h->ws.get("gw_flags", sizeof(uint32_t) * 4, st);
+  ga.flags = gflags;
+  ga.cv_n = gflags + 1;
+  ga.ovf_n = gflags + 2;
+  ga.ovf_cap = std::min<uint32_t>(kb, 1u << 16);
+  ga.ovf_keys = (uint32_t*)h->ws.get("gw_ovf_keys", sizeof(uint32_t) * ga.ovf_cap, st);
+  ga.match_n = gflags + 3;
+  // carry: at most `cap` entries per key from the LDS rings, and a redone key's whole list -- room for 4M of those
+  // (more sends the push to the tiled path)
+  ga.cv_cap = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(nt, (int64_t)kb * gp.cap + (1 << 22)));
+  ga.cv_ts = (int64_t*)h->ws.get("cv_ts", sizeof(int64_t) * (size_t)ga.cv_cap, st);
+  ga.cv_val = (int64_t*)h->ws.get("cv_val", sizeof(int64_t) * (size_t)ga.cv_cap, st);
+  ga.cv_pay = (int64_t*)h->ws.get("cv_pay", sizeof(int64_t) * (size_t)ga.cv_cap, st);
+  ga.cv_key = (int32_t*)h->ws.get("cv_key", sizeof(int32_t) * (size_t)ga.cv_cap, st);
+  HIPCHK(hipMemsetAsync(gflags, 0, sizeof(uint32_t) * 4, st));
+  HIPCHK(hipMemsetAsync(ga.trig, 0, sizeof(uint64_t) * ((size_t)n + 1), st));
+  h->kbeg("group_walk");
+  dispatch_op(op, [&](auto opc) { launch_gwalk<T, decltype(opc)::value>(ga, ng, st); });
+  h->kend();
+  uint32_t hf[4] = {0, 0, 0, 0}, total = 0;
+  HIPCHK(hipMemcpyAsync(hf, gflags, sizeof(hf), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (hf[0] & GW_INTERNAL) throw SgError(SG_EINVAL, "internal: group walker guard tripped");
+  if (hf[0]) return 0;   // a key whose time goes back (or more ring overflows than the list holds): the tiled path
+  if (hf[2]) {
+    // keys whose pending list outgrew the LDS ring: each walked again with an unbounded HBM list
+    h->kbeg("gw_redo");
+    uint32_t* rrows = (uint32_t*)h->ws.get("gw_redo_rows", sizeof(uint32_t) * (size_t)nt, st);
+    char* rl = (char*)h->ws.get("gw_redo_list", (sizeof(T) + 8) * (size_t)nt, st);
+    T* hv = (T*)rl;
+    int32_t* ht = (int32_t*)(rl + sizeof(T) * (size_t)nt);
+    int32_t* hp = ht + nt;
+    dispatch_op(op, [&](auto opc) { launch_gw_redo<T, decltype(opc)::value>(ga, hf[2], rrows, hv, ht, hp, st); });
+    h->kend();
+    HIPCHK(hipMemcpyAsync(hf, gflags, sizeof(hf), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (hf[0] & GW_INTERNAL) throw SgError(SG_EINVAL, "internal: group walker redo guard tripped");
+    if (hf[0]) return 0;
+  }
+  // (last decline point: from here on the push is delivered)
+  h->last_spilled = hf[2];
+  total = hf[3];   // matches, counted by the walkers
+  h->mark(3);
+  h->split_out = 1;
+  h->mark(5);
+  if (total) {
+    GwSel sel = gp.sel;
+    recv_slot(d, d.shape_args[1], sel.multi, sel.b_slot);
+    sel.pzero = v.pfloat;
+    gw_project(h, bv, n, ga, sel, total);
+  }
+  h->mark(4);
+  if (ga.carry_out) {
+    WalkArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.alive = (uint32_t*)h->ws.get("alive_rows", sizeof(uint32_t), st);
+    wa.alive_n = (uint32_t*)h->ws.get("gw_alive_n", sizeof(uint32_t), st);
+    HIPCHK(hipMemsetAsync(wa.alive_n, 0, sizeof(uint32_t), st));
+    wa.cv_n = ga.cv_n;
+    wa.cv_ts = ga.cv_ts;
+    wa.cv_key = ga.cv_key;
+    wa.cv_val = ga.cv_val;
+    wa.cv_pay = ga.cv_pay;
+    carry_out_rows<T, true>(h, es, nt, v, bv, cc, wa, val_col_a, v.pcol ? plan.pcol : -1, v.pw);
+  }
+  h->last_events = n;
+  h->last_matches = total;
+  return 1;
+}

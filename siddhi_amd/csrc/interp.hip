@@ -23,14 +23,9 @@
 
 #include "sg_device.h"
 #include "sg_engine.h"
+#include "sg_prim.h"
 #include "interp.h"
 #include "pred.h"
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 struct GeneralState {
   SgGeo geo;
@@ -444,13 +439,8 @@ static uint32_t general_key_bound(SgHandle* h, const BatchView& bv, int64_t n) {
     kb = bv.key_bound > 0 ? (uint32_t)bv.key_bound : 0;
     if (kb == 0) {
       int32_t* dmax = (int32_t*)h->ws.get("kmax", sizeof(int32_t), st);
-      size_t tb = 0;
-      HIPCHK(rocprim::reduce(nullptr, tb, bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>(), st));
-      void* tmp = h->ws.get("kmax_tmp", tb, st);
-      HIPCHK(rocprim::reduce(tmp, tb, bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>(), st));
-      int32_t hm = 0;
-      HIPCHK(hipMemcpyAsync(&hm, dmax, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      sg_reduce(h->ws, st, "kmax_tmp", bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>());
+      int32_t hm = sg_read_back(dmax, st);
       kb = (uint32_t)(hm + 1);
     }
   }
@@ -580,12 +570,7 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
   h->kend();
   h->mark(1);
   h->kbeg("key_sort");
-  {
-    size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys, rows, srows, (size_t)n, 0, end_bit, st));
-    void* tmp = h->ws.get("g_sort_tmp", tb, st);
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, keys, skeys, rows, srows, (size_t)n, 0, end_bit, st));
-  }
+  sg_radix_sort_pairs(h->ws, st, "g_sort_tmp", keys, skeys, rows, srows, (size_t)n, end_bit);
   uint32_t* beg = (uint32_t*)h->ws.get("g_beg", sizeof(uint32_t) * kb, st);
   uint32_t* end = (uint32_t*)h->ws.get("g_end", sizeof(uint32_t) * kb, st);
   HIPCHK(hipMemsetAsync(beg, 0, sizeof(uint32_t) * kb, st));
@@ -635,19 +620,11 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
     int64_t* clk = (int64_t*)h->ws.get("g_clk", sizeof(int64_t) * n, st);
     uint32_t* rev = (uint32_t*)h->ws.get("g_fire_rev", sizeof(uint32_t) * n, st);
     uint32_t* nfr = (uint32_t*)h->ws.get("g_fire_next", sizeof(uint32_t) * n, st);
-    size_t tb = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, tb, bv.ts, clk, (size_t)n, rocprim::maximum<int64_t>(), st));
-    void* tmp = h->ws.get("g_clk_tmp", tb, st);
-    HIPCHK(rocprim::inclusive_scan(tmp, tb, bv.ts, clk, (size_t)n, rocprim::maximum<int64_t>(), st));
+    sg_inclusive_scan(h->ws, st, "g_clk_tmp", bv.ts, clk, (size_t)n, rocprim::maximum<int64_t>());
     hipLaunchKernelGGL(k_fire_rev, grd, blk, 0, st, n, bv.ts, clk, gs->clock, rev);
     HIPCHK(hipGetLastError());
-    tb = 0;
-    HIPCHK(rocprim::inclusive_scan(nullptr, tb, rev, nfr, (size_t)n, rocprim::minimum<uint32_t>(), st));
-    tmp = h->ws.get("g_nfr_tmp", tb, st);
-    HIPCHK(rocprim::inclusive_scan(tmp, tb, rev, nfr, (size_t)n, rocprim::minimum<uint32_t>(), st));
-    int64_t last = 0;
-    HIPCHK(hipMemcpyAsync(&last, clk + (n - 1), sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_inclusive_scan(h->ws, st, "g_nfr_tmp", rev, nfr, (size_t)n, rocprim::minimum<uint32_t>());
+    int64_t last = sg_read_back(clk + (n - 1), st);
     na.clk = clk;
     na.nfr = nfr;
     next_clock = std::max(gs->clock, last);
@@ -727,13 +704,8 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
     uint32_t* nch = (uint32_t*)h->ws.get("g_nch", sizeof(uint32_t) * (kb + 1), st);
     uint32_t* uoff = (uint32_t*)h->ws.get("g_uoff", sizeof(uint32_t) * (kb + 1), st);
     hipLaunchKernelGGL(k_unit_count, dim3((unsigned)((kb + 1 + 255) / 256)), blk, 0, st, (int64_t)kb, beg, end, R, nch);
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, nch, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>(), st));
-    void* tmp = h->ws.get("g_uscan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, nch, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t U = 0;
-    HIPCHK(hipMemcpyAsync(&U, uoff + kb, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_exclusive_scan(h->ws, st, "g_uscan_tmp", nch, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
+    uint32_t U = sg_read_back(uoff + kb, st);
     const size_t kw = (size_t)gs->geo.key_words;
     UnitArgs ua;
     ua.R = R;
@@ -796,10 +768,7 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
     HIPCHK(hipGetLastError());
     int sbits = 31 + 1 + kbits;
     if (sbits > 64) sbits = 64;
-    size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, sk, sk2, ix, ix2, (size_t)total, 0, sbits, st));
-    void* tmp = h->ws.get("g_sort2_tmp", tb, st);
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, sk, sk2, ix, ix2, (size_t)total, 0, sbits, st));
+    sg_radix_sort_pairs(h->ws, st, "g_sort2_tmp", sk, sk2, ix, ix2, (size_t)total, sbits);
     char* out = h->out.reserve((int64_t)total, d.n_select, st);
     int32_t ostride = 32 + 8 * d.n_select;
     hipLaunchKernelGGL(k_gather, g2, blk, 0, st, (int64_t)total, ebuf, stride, ix2, out + (size_t)h->out.n * ostride,

@@ -47,12 +47,6 @@
 #include "router.h"
 #include "sg_engine.h"
 
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 struct sg_handle {   // (api.hip's definition)
   SgHandle h;
 };

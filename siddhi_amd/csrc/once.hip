@@ -36,12 +36,7 @@
 #include "pred.h"
 #include "sg_device.h"
 #include "sg_engine.h"
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+#include "sg_prim.h"
 
 namespace {
 
@@ -265,13 +260,8 @@ void sg_run_once(SgHandle* h, const BatchView& bv, int64_t n) {
     kb = bv.key_bound > 0 ? (uint32_t)bv.key_bound : 0;
     if (kb == 0 && n > 0) {
       int32_t* dmax = (int32_t*)h->ws.get("kmax", sizeof(int32_t), st);
-      size_t tb = 0;
-      HIPCHK(rocprim::reduce(nullptr, tb, bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>(), st));
-      void* tmp = h->ws.get("kmax_tmp", tb, st);
-      HIPCHK(rocprim::reduce(tmp, tb, bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>(), st));
-      int32_t hm = 0;
-      HIPCHK(hipMemcpyAsync(&hm, dmax, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      sg_reduce(h->ws, st, "kmax_tmp", bv.key, dmax, (int32_t)-1, (size_t)n, rocprim::maximum<int32_t>());
+      int32_t hm = sg_read_back(dmax, st);
       kb = (uint32_t)std::max(hm + 1, 1);
     }
     kb = std::max<uint32_t>(kb, 1);
@@ -372,10 +362,7 @@ void sg_run_once(SgHandle* h, const BatchView& bv, int64_t n) {
     int end_bit = 1;
     while (end_bit < 32 && (1ull << end_bit) <= (uint64_t)n) ++end_bit;
     h->kbeg("once_order");
-    size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, prow, srow, pkey, skey, (size_t)m, 0, end_bit, st));
-    void* tmp = h->ws.get("once_sort_tmp", tb, st);
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, prow, srow, pkey, skey, (size_t)m, 0, end_bit, st));
+    sg_radix_sort_pairs(h->ws, st, "once_sort_tmp", prow, srow, pkey, skey, (size_t)m, end_bit);
     // group: one match per trigger (rank 0); a Multi receiver reports the visit slot of B (eventSequence = reversed
     // init order), as the other routes do
     const int rb = d.recv_of_stream[d.states[b_state].stream];

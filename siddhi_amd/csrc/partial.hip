@@ -32,16 +32,11 @@
 
 #include "sg_device.h"
 #include "sg_engine.h"
+#include "sg_prim.h"
 #include "interp.h"
 #include "chain.h"
 #include "seq.h"
 #include "pred.h"
-
-#define HIPCHK(x)                                                                                   \
-  do {                                                                                              \
-    hipError_t e_ = (x);                                                                            \
-    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // Carried rows: SoA in the batch's own column formats (so the general machine can replay them as a batch).
 struct PpRows {
@@ -852,11 +847,7 @@ int64_t sg_partial_carried(const PartialState* ps) { return ps->rows[ps->cur].n;
 
 static void sort_pairs64(SgHandle* h, const char* tag, uint64_t* k_in, uint64_t* k_out, uint32_t* v_in, uint32_t* v_out,
                          int64_t n, int end_bit) {
-  hipStream_t st = h->stream;
-  size_t tb = 0;
-  HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, st));
-  void* tmp = h->ws.get(std::string("pp_sorttmp_") + tag, tb, st);
-  HIPCHK(rocprim::radix_sort_pairs(tmp, tb, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, st));
+  sg_radix_sort_pairs(h->ws, h->stream, std::string("pp_sorttmp_") + tag, k_in, k_out, v_in, v_out, (size_t)n, end_bit);
 }
 
 // ---- sequence lanes (seq.h): one lane per key resumes the key's compact machine over its rows ----------------------
@@ -1279,15 +1270,8 @@ static int seq_lanes_push(SgHandle* h, PartialState* ps, const BatchView& bv, in
   const dim3 gk((unsigned)((kb + 1 + 255) / 256));
   h->kbeg("sequence_units");
   hipLaunchKernelGGL(k_sq_ucount, gk, blk, 0, st, (int64_t)kb, beg, end, sids, a.nc, pl_.R, ncar, nu);
-  {
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, nu, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>(), st));
-    void* tmp = h->ws.get("sq_uscan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, nu, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>(), st));
-  }
-  uint32_t U = 0;
-  HIPCHK(hipMemcpyAsync(&U, uoff + kb, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  sg_exclusive_scan(h->ws, st, "sq_uscan_tmp", nu, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
+  uint32_t U = sg_read_back(uoff + kb, st);
   uint32_t* umap = (uint32_t*)h->ws.get("sq_umap", 4 * ((size_t)U + 1), st);
   hipLaunchKernelGGL(k_sq_umap, dim3((unsigned)((kb + 255) / 256)), blk, 0, st, (int64_t)kb, uoff, umap);
   pl_.beg = beg;
@@ -1376,10 +1360,7 @@ static int seq_lanes_push(SgHandle* h, PartialState* ps, const BatchView& bv, in
     uint64_t* kb2 = (uint64_t*)h->ws.get("sq_kb", 8 * R, st);
     h->kbeg("match_order");
     hipLaunchKernelGGL(k_pp_iota, g2, blk, 0, st, R, ia);
-    size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, o.k1, kb2, ia, ib, (size_t)R, 0, k1_bits, st));
-    void* tmp = h->ws.get("sq_sorttmp", tb, st);
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, o.k1, kb2, ia, ib, (size_t)R, 0, k1_bits, st));
+    sg_radix_sort_pairs(h->ws, st, "sq_sorttmp", o.k1, kb2, ia, ib, (size_t)R, k1_bits);
     char* out = h->out.reserve(total, nsel, st);
     // records built in slot order (a lane's slots hold one key's matches: the compact records and the packed rows they
     // name are read nearly in order) and scattered to their delivery positions (k_em_scatter), as the partial lanes do
@@ -1419,13 +1400,8 @@ static void carry_rows(SgHandle* h, PartialState* ps, const BatchView& bv, const
     h->kbeg("carry");
     uint32_t* pos = (uint32_t*)h->ws.get("pp_pos", 4 * (m + 1), st);
     HIPCHK(hipMemsetAsync(keep + m, 0, 4, st));
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, keep, pos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>(), st));
-    void* tmp = h->ws.get("pp_scan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, keep, pos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>(), st));
-    uint32_t nn = 0;
-    HIPCHK(hipMemcpyAsync(&nn, pos + m, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_exclusive_scan(h->ws, st, "pp_scan_tmp", keep, pos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>());
+    uint32_t nn = sg_read_back(pos + m, st);
     PpRows& nr = ps->rows[1 - ps->cur];
     rows_reserve(ps, nr, nn);
     PpCopyCols c2;
@@ -1498,13 +1474,8 @@ int sg_partial_push(SgHandle* h, PartialState* ps, const BatchView& bv, int64_t 
     // the largest timestamp so far; every later row is at most max_lateness_ms behind it, so a partial whose e1 is
     // more than `within` before (that - max_lateness_ms) never sees a row it could emit at again
     int64_t* dmax = (int64_t*)h->ws.get("pp_tsmax", sizeof(int64_t), st);
-    size_t tb = 0;
-    HIPCHK(rocprim::reduce(nullptr, tb, bv.ts, dmax, INT64_MIN, (size_t)n, rocprim::maximum<int64_t>(), st));
-    void* tmp = h->ws.get("pp_tsmax_tmp", tb, st);
-    HIPCHK(rocprim::reduce(tmp, tb, bv.ts, dmax, INT64_MIN, (size_t)n, rocprim::maximum<int64_t>(), st));
-    int64_t hm = INT64_MIN;
-    HIPCHK(hipMemcpyAsync(&hm, dmax, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    sg_reduce(h->ws, st, "pp_tsmax_tmp", bv.ts, dmax, INT64_MIN, (size_t)n, rocprim::maximum<int64_t>());
+    int64_t hm = sg_read_back(dmax, st);
     h->ts_max_seen = std::max(h->ts_max_seen, hm);
     const int64_t lat = std::max<int64_t>(0, h->opt.max_lateness_ms);
     const int64_t w = std::max<int64_t>(0, d.within);
@@ -1596,9 +1567,7 @@ int sg_partial_push(SgHandle* h, PartialState* ps, const BatchView& bv, int64_t 
     ra.partitioned = d.partitioned;
     ra.sentinel = sentinel;
     for (int k = 0; k < SG_MAX_RET; ++k) ra.hot[k] = ps->hot[k];
-    int64_t t0 = 0;
-    HIPCHK(hipMemcpyAsync(&t0, n ? bv.ts : cr.ts, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int64_t t0 = sg_read_back<int64_t>(n ? bv.ts : cr.ts, st);
     ra.tbase = t0;
     PpRec* recs = (PpRec*)h->ws.get("pp_recs", sizeof(PpRec) * m, st);
     PpRec* srecs = (PpRec*)h->ws.get("pp_srecs", sizeof(PpRec) * m, st);
@@ -1607,16 +1576,9 @@ int sg_partial_push(SgHandle* h, PartialState* ps, const BatchView& bv, int64_t 
     HIPCHK(hipGetLastError());
     h->kend();
     h->kbeg("key_sort");
-    {
-      size_t tb = 0;
-      HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys, recs, srecs, (size_t)m, 0, end_bit, st));
-      void* tmp = h->ws.get("pp_rsort_tmp", tb, st);
-      HIPCHK(rocprim::radix_sort_pairs(tmp, tb, keys, skeys, recs, srecs, (size_t)m, 0, end_bit, st));
-    }
+    sg_radix_sort_pairs(h->ws, st, "pp_rsort_tmp", keys, skeys, recs, srecs, (size_t)m, end_bit);
     h->kend();
-    int32_t herr = 0;
-    HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int32_t herr = sg_read_back(err, st);
     if (herr & 2) throw SgError(SG_EINVAL, "a partition key id is >= the batch's key_bound");
     if (herr & 4) {   // a timestamp more than 2^31 ms from the push's first: the gather path carries full timestamps
       rec_mode = false;
@@ -1644,12 +1606,7 @@ int sg_partial_push(SgHandle* h, PartialState* ps, const BatchView& bv, int64_t 
     HIPCHK(hipGetLastError());
     h->kend();
     h->kbeg("key_sort");
-    {
-      size_t tb = 0;
-      HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, keys, skeys, ids, sids, (size_t)m, 0, end_bit, st));
-      void* tmp = h->ws.get("pp_sort_tmp", tb, st);
-      HIPCHK(rocprim::radix_sort_pairs(tmp, tb, keys, skeys, ids, sids, (size_t)m, 0, end_bit, st));
-    }
+    sg_radix_sort_pairs(h->ws, st, "pp_sort_tmp", keys, skeys, ids, sids, (size_t)m, end_bit);
     HIPCHK(hipMemsetAsync(beg, 0, 4 * (size_t)kb, st));
     HIPCHK(hipMemsetAsync(end, 0, 4 * (size_t)kb, st));
     if (m) hipLaunchKernelGGL(k_pp_segments, grd, blk, 0, st, m, a, skeys, sids, (const int64_t*)nullptr,
@@ -1663,27 +1620,18 @@ int sg_partial_push(SgHandle* h, PartialState* ps, const BatchView& bv, int64_t 
     h->kend();
   }
   {
-    int32_t herr = 0;
-    HIPCHK(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    int32_t herr = sg_read_back(err, st);
     if (herr & 2) throw SgError(SG_EINVAL, "a partition key id is >= the batch's key_bound");
   }
   h->mark(2);
   if (ps->mode == 2) return seq_lanes_push(h, ps, bv, n, kb, a, P, skeys, sids, beg, end, sentinel);
   h->kbeg("start_rows");
   HIPCHK(hipMemsetAsync(flag + m, 0, 4, st));
-  {
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, flag, fpos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>(), st));
-    void* tmp = h->ws.get("pp_fscan_tmp", tb, st);
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, flag, fpos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>(), st));
-  }
+  sg_exclusive_scan(h->ws, st, "pp_fscan_tmp", flag, fpos, (uint32_t)0, (size_t)m + 1, rocprim::plus<uint32_t>());
   if (m) hipLaunchKernelGGL(k_pp_compact, grd, blk, 0, st, m, flag, fpos, cand);
   HIPCHK(hipGetLastError());
   h->kend();
-  uint32_t ncand = 0;
-  HIPCHK(hipMemcpyAsync(&ncand, fpos + m, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  uint32_t ncand = sg_read_back(fpos + m, st);
   // ---- partial lanes
   const int nsel = d.n_select;
   const int32_t rstride = 32 + 8 * nsel;

@@ -21,6 +21,21 @@ struct SgError {
   SgError(int c, std::string m) : code(c), msg(std::move(m)) {}
 };
 
+#define HIPCHK(x)                                                                                   \
+  do {                                                                                              \
+    hipError_t e_ = (x);                                                                            \
+    if (e_ != hipSuccess) throw SgError(SG_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+// one value of HBM on the host, after everything queued on the stream so far
+template <class T>
+static T sg_read_back(const T* dp, hipStream_t st) {
+  T v;
+  HIPCHK(hipMemcpyAsync(&v, dp, sizeof(T), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return v;
+}
+
 // Named, grow-only device workspaces (no allocation in steady state).
 struct Workspace {
   struct Buf { void* p = nullptr; size_t bytes = 0; };

@@ -1,12 +1,12 @@
 """The group walker's routes and edges (csrc/gwalk.h: k_gwalk, k_gw_redo, k_gtile_count, k_gscan_project; the wide
-partition in front of it, engine_impl.h part1_wide) on small batches with sparse key ids, row for row against the oracle.
+partition in front of it, keypart.h part1_wide) on small batches with sparse key ids, row for row against the oracle.
 
 The gate of that path is the key *bound* (`key.max() + 1`, and the engine keeps the largest bound seen), not the number
 of keys: a batch of 20,000 rows in which one row carries key id 69,999 takes the wide partition and the group walker,
 and the oracle (a map over the ids) does not care.  So every case here is a few 10^4 rows and every handle sees at
 least one key id >= 65,536.
 
-A push the group walker declines is run again on the tiled walker and passes parity all the same, so every case also
+A push the group walker declines goes on to the tiled walker and passes parity all the same, so every case also
 asserts, push by push, which route ran -- from the names of the kernels the handle timed (timing().kernels()) and
 timing().spilled_units:
 
@@ -14,10 +14,13 @@ timing().spilled_units:
                   oracle delivers a match for the push -- "gw_project" wrote it
   redone(k)       WALKED, "gw_redo" ran and spilled_units == k (redone(): >= 1)
   DECLINED        "group_walk" ran and "gw_project" did not: k_gwalk (or k_gw_redo) raised GW_ORDER / GW_OVERFLOW and the
-                  push ran again on the tiled walker
+                  tiled walker took the push
   DECLINED_EARLY  "gw_count" ran, "group_walk" did not, and the tiled walker's "walk_count" did: run_group_walk read the
-                  partition's pack flags (PK_PAY_RANGE, PK_TS_RANGE) after part1_wide and k_gw_count had run and returned
-                  before launching k_gwalk
+                  partition's pack flag PK_PAY_RANGE after part1_wide and k_gw_count had run and returned before
+                  launching k_gwalk
+  DECLINED_WIDE   as DECLINED_EARLY, for PK_TS_RANGE: the whole push runs again with wide records
+                  DECLINED and DECLINED_EARLY go on with pass 2 of the partition from the records pass 1 left, so
+                  "pred" and "part_group" are each timed exactly once in such a push
   NOT_TRIED       neither "gw_count" nor "group_walk": gw_plan said no before any launch, or the partition was not the
                   wide one
 
@@ -36,6 +39,7 @@ pytestmark = pytest.mark.gpu
 T0 = 1_700_000_000_000
 DAY = 86_400_000
 WALKED, DECLINED, DECLINED_EARLY, NOT_TRIED = "walked", "declined", "declined_early", "not_tried"
+DECLINED_WIDE = "declined_wide"
 
 
 def redone(k=None):
@@ -100,12 +104,15 @@ def check_route(route, names, spilled, emitted, where):
             assert spilled >= 1 if route[1] is None else spilled == route[1], msg
     elif route == DECLINED:
         assert "group_walk" in names and "gw_project" not in names, msg
-    elif route == DECLINED_EARLY:
+    elif route in (DECLINED_EARLY, DECLINED_WIDE):
         assert "gw_count" in names and "group_walk" not in names and "gw_project" not in names and tiled, msg
     elif route == NOT_TRIED:
         assert "group_walk" not in names and "gw_count" not in names and "gw_project" not in names, msg
     else:
         raise ValueError(route)
+    if route in (DECLINED, DECLINED_EARLY):
+        # the tiled walker goes on from pass 1's records: the predicate pass and pass 1 of the partition ran once
+        assert names.count("pred") == 1 and names.count("part_group") == 1, msg
 
 
 def drive(make, q, batches, fetch_after=None, restore_after=()):
@@ -567,7 +574,7 @@ def test_decline_payload_past_32_bits():
 def test_decline_time_span_past_31_bits():
     """PK_TS_RANGE (run_group_walk returns 2: wide records): push 2 comes 30 days after push 1, so its first carried row
     lies more than 2^31 ms before its rows.  The code reads the pack flags before it launches k_gwalk, so "group_walk"
-    is absent while "gw_count" ran: DECLINED_EARLY, on every run.  Every key gets rows in push 2, which drops its
+    is absent while "gw_count" ran: DECLINED_WIDE, on every run.  Every key gets rows in push 2, which drops its
     30-day-old partials; push 3 follows at once: WALKED."""
     rng = np.random.default_rng(19)
     n = 20_000
@@ -575,7 +582,7 @@ def test_decline_time_span_past_31_bits():
     b1 = ordinary(rng, keys, n, T0, 0)
     b2 = ordinary(rng, keys, n, T0 + 30 * DAY, n)
     b3 = ordinary(rng, keys, n, T0 + 30 * DAY + 500, 2 * n)
-    want, per = parity(query(), [b1, b2, b3], [WALKED, DECLINED_EARLY, WALKED], min_matches=10_000)
+    want, per = parity(query(), [b1, b2, b3], [WALKED, DECLINED_WIDE, WALKED], min_matches=10_000)
     assert per[2] > 1000 and (want.vals[per[0] + per[1]:, 0] < 2 * n).any()   # push 3 completes partials of push 2
 
 

@@ -1,4 +1,4 @@
-"""GPU parity for the two key-partition paths of the closed-form walker (siddhi_amd/csrc/engine_impl.h): the
+"""GPU parity for the two key-partition paths of the closed-form walker (siddhi_amd/csrc/keypart.h): the
 LDS-staged counting partition (one pass for key_bound <= 256, two passes up to 65536) and the rocPRIM radix
 sort (sg_options.partition_sort = 1, and every key_bound above 65536).  Both must hand the walkers each key's
 rows in arrival order -- the routing of PartitionStreamReceiver (C/partition/PartitionStreamReceiver.java:80-281)

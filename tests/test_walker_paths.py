@@ -1,4 +1,4 @@
-"""GPU parity for every code path of the closed-form every->next walker (siddhi_amd/csrc/engine_impl.h):
+"""GPU parity for every code path of the closed-form every->next walker (siddhi_amd/csrc/walk.h, driven by engine_impl.h):
 the monotone-stack and scanned-list pending lists, all four compare operators, all four value types,
 the HBM-list overflow path (pending list deeper than the LDS ring, and units spanning > 2^31 ms), null
 handling of compared and projected attributes, and multi-push carry in each mode.  Every case is checked
@@ -244,7 +244,7 @@ def test_wide_payload_in_later_push():
     check(app, split(b, [30_000]))
 
 
-# ---- unpartitioned streams: per-candidate search (engine_impl.h k_nge) and its fallback to the walker
+# ---- unpartitioned streams: per-candidate search (walk.h k_nge) and its fallback to the walker
 
 @pytest.mark.parametrize("cond", ["price > e1.price", "price >= e1.price and volume > 400", "price < e1.price"])
 @pytest.mark.parametrize("walker_only", [False, True])

@@ -1,4 +1,4 @@
-"""The closed form's key partition beyond 65,536 keys (engine_impl.h part1_wide: pass 1 in two LDS counting passes,
+"""The closed form's key partition beyond 65,536 keys (keypart.h part1_wide: pass 1 in two LDS counting passes,
 supergroups then groups of 256 keys, up to 4096 groups) and the arrival-order carry (k_carry_mark / k_carry_bcount /
 k_carry_gather) -- row for row against the oracle (the C++ restatement of StreamPreStateProcessor.processAndReturn,
 C/query/input/stream/state/StreamPreStateProcessor.java:292-337), over key bounds on both sides of the wide path's
