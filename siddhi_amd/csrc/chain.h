@@ -97,7 +97,7 @@ struct SgPpRule {
   int32_t nterm[PP_MAX_S];            // -1: the VM evaluates the state's filter
   PpTerm term[PP_MAX_S][PP_MAX_TERMS];
   PpWait wait[PP_MAX_S];
-  uint32_t wait_slots;                // retained slots some wait term reads (block summaries, partial.hip)
+  uint32_t wait_slots;                // retained slots some wait term reads (block summaries, pp_lanes.h)
 };
 
 // Parse a postfix filter into conjunctive compare terms (t1 t2 AND t3 AND ...); false if it has another form.

@@ -486,7 +486,8 @@ void sg_run_general(SgHandle* h, const BatchView& bv, int64_t n) {
       lo += cnt;
     }
     if (lo == n) return;
-    // the route declined a push before anything was carried (sg_partial_push, seq_lanes_push): the per-key machine
+    // the route declined a push before anything was carried (partial.hip sg_partial_push, sq_lanes.h seq_lanes_push):
+    // the per-key machine
     // takes the stream from here, exactly
     if (sg_partial_carried(gs->pp)) throw SgError(SG_EUNSUPPORTED, "partial-lane route left with carried partials");
     sg_partial_deactivate(gs->pp);
@@ -524,6 +525,137 @@ static bool grown_geo(const sg_nfa_desc& d, const SgGeo& g, SgGeo& ng) {
   auto up = [&](int32_t x) { return (int32_t)std::min<int64_t>(lim, std::max<int64_t>(4, (int64_t)x * 4)); };
   ng = sg_make_geo(d, up(g.P), up(g.E), up(g.C), up(g.L), up(g.Q));
   return ng.key_words < ((int64_t)1 << 31);
+}
+
+// What the attempts of one push share; cap grows between them, ebuf and total are the last attempt's.
+struct MachinePush {
+  uint32_t kb;
+  int kbits;
+  SgChunkRule rule;
+  bool ts_monotone;
+  int64_t span;               // last timestamp of the push - first
+  int64_t cap;                // emission space, in matches
+  char* ebuf;
+  unsigned long long total;
+};
+
+// Rows per unit when the push is cut into (key, chunk of R rows) units; 0: one unit per key.
+static uint32_t unit_rows(SgHandle* h, const GeneralState* gs, const MachinePush& mp, int64_t n) {
+  const sg_nfa_desc& d = h->desc;
+  const SgChunkRule& rule = mp.rule;
+  // A time-horizon unit's runtime is rebuilt from the rows inside `within` before its chunk, so it lacks the partials
+  // parked in a count state since before that horizon: they never expire (CountPreStateProcessor.processAndReturn,
+  // C/query/input/stream/state/CountPreStateProcessor.java:53-93) and a later push whose time goes back can complete
+  // them -- queries with a count state are cut only by the sequence's event horizon
+  const bool count_q = has_count_state(d);
+  if (rule.kind == 0 || !(rule.kind == 2 || (mp.ts_monotone && !count_q)) || h->opt.chunk_rows < 0 || n <= 0) return 0;
+  if (h->opt.chunk_rows > 0) return (uint32_t)h->opt.chunk_rows;
+  // horizon rows per unit (rows of an average key inside `within`, or the sequence's event horizon);
+  // units at least 4x their horizon, enough of them to fill the chip, scratch arenas within budget
+  const int64_t span = std::max<int64_t>(1, mp.span);
+  const double per_key = (double)n / (double)std::max<uint32_t>(mp.kb, 1);
+  const double hz = rule.kind == 2 ? (double)rule.events : per_key * (double)rule.within / (double)span;
+  // (measured on C3b/C3c: 131k -> 524k units took 372 -> 245 ms and 3150 -> 2347 ms per 100M events;
+  // 1M units gained nothing more)
+  const int64_t target_units = 256 * 32 * 64;
+  const int64_t mem_units = std::max<int64_t>(1, ((int64_t)24 << 30) / ((int64_t)gs->geo.key_words * 4));
+  int64_t r = std::max<int64_t>({(int64_t)(4.0 * hz) + 1, 32, (n + target_units - 1) / target_units,
+                                 (n + mem_units - 1) / mem_units});
+  const uint32_t R = (uint32_t)std::min<int64_t>(r, 1 << 30);
+  return (double)R >= per_key * 2.0 ? 0 : R;   // (0: hardly any key would be cut)
+}
+
+// the per-key machines over (key, chunk of R rows) units
+static void launch_units(SgHandle* h, GeneralState* gs, const BatchView& bv, const NfaArgs& na, const MachinePush& mp,
+                         uint32_t R, const SgEmitSink& sink) {
+  hipStream_t st = h->stream;
+  const uint32_t kb = mp.kb;
+  const dim3 blk(256);
+  uint32_t* nch = (uint32_t*)h->ws.get("g_nch", sizeof(uint32_t) * (kb + 1), st);
+  uint32_t* uoff = (uint32_t*)h->ws.get("g_uoff", sizeof(uint32_t) * (kb + 1), st);
+  hipLaunchKernelGGL(k_unit_count, dim3((unsigned)((kb + 1 + 255) / 256)), blk, 0, st, (int64_t)kb, na.beg, na.end, R, nch);
+  sg_exclusive_scan(h->ws, st, "g_uscan_tmp", nch, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
+  uint32_t U = sg_read_back(uoff + kb, st);
+  const size_t kw = (size_t)gs->geo.key_words;
+  UnitArgs ua;
+  ua.R = R;
+  ua.rule = mp.rule;
+  ua.n_units = U;
+  ua.uoff = uoff;
+  uint32_t* umap = (uint32_t*)h->ws.get("g_umap", sizeof(uint32_t) * std::max<uint32_t>(U, 1), st);
+  ua.umap = umap;
+  ua.scratch = (int32_t*)h->ws.get("g_uarena", sizeof(int32_t) * kw * std::max<uint32_t>(U, 1), st);
+  int32_t* snap = (int32_t*)h->ws.get("g_snap", sizeof(int32_t) * kw * kb, st);
+  HIPCHK(hipMemcpyAsync(snap, gs->arena, sizeof(int32_t) * kw * kb, hipMemcpyDeviceToDevice, st));
+  ua.snap = snap;
+  hipLaunchKernelGGL(k_unit_map, dim3((unsigned)((kb + 255) / 256)), blk, 0, st, (int64_t)kb, uoff, umap);
+  h->kbeg("nfa_units");
+  if (U)
+    hipLaunchKernelGGL(k_nfa_units, dim3((unsigned)((U + 63) / 64)), dim3(64), 0, st, na, ua, bv.cols, h->ddesc,
+                       gs->dgeo, gs->arena, sink, gs->dfail);
+  h->kend();
+  hipLaunchKernelGGL(k_unit_keep, dim3((unsigned)std::min<uint32_t>(std::max<uint32_t>(kb, 1), 65535)), blk, 0, st,
+                     (int64_t)kb, uoff, ua.scratch, gs->dgeo, gs->arena);
+}
+
+// One attempt of the push over the per-key machines with mp.cap matches of emission space.  Returns true when it
+// stands (mp.ebuf, mp.total); false when a key's pools or the emission space ran out: the arenas are rolled back, the
+// capacity that ran out is 4x, and the push is to be run again.
+static bool machine_attempt(SgHandle* h, GeneralState* gs, const BatchView& bv, const NfaArgs& na, MachinePush& mp,
+                            int attempt) {
+  const sg_nfa_desc& d = h->desc;
+  hipStream_t st = h->stream;
+  const uint32_t kb = mp.kb;
+  const int32_t stride = sg_emit_stride(d.n_select);
+  unsigned long long* ecount = (unsigned long long*)h->ws.get("g_ecount", 16, st);
+  int32_t* eover = (int32_t*)h->ws.get("g_eover", 4, st);
+  const size_t pre_bytes = (size_t)kb * (size_t)gs->geo.key_words * 4;
+  int32_t* pre = (int32_t*)h->ws.get("g_pre", std::max<size_t>(pre_bytes, 4), st);
+  if (pre_bytes) HIPCHK(hipMemcpyAsync(pre, gs->arena, pre_bytes, hipMemcpyDeviceToDevice, st));
+  mp.ebuf = (char*)h->ws.get("g_emit", (size_t)mp.cap * stride, st);
+  HIPCHK(hipMemsetAsync(ecount, 0, 8, st));
+  HIPCHK(hipMemsetAsync(eover, 0, 4, st));
+  HIPCHK(hipMemsetAsync(gs->dfail, 0, 4, st));
+  SgEmitSink sink;
+  sink.buf = mp.ebuf;
+  sink.cap = mp.cap;
+  sink.count = ecount;
+  sink.overflow = eover;
+  sink.stride = stride;
+  sink.key_bits = mp.kbits;
+  // ---- unit plan: one unit per key, or (chunkable shapes) per (key, chunk of R rows)
+  const uint32_t R = unit_rows(h, gs, mp, na.n);
+  if (R > 0) {
+    launch_units(h, gs, bv, na, mp, R, sink);
+  } else {
+    h->kbeg("nfa_keys");
+    hipLaunchKernelGGL(k_nfa, dim3((unsigned)((kb + 63) / 64)), dim3(64), 0, st, na, bv.cols, h->ddesc, gs->dgeo,
+                       gs->arena, sink, gs->dfail);
+    h->kend();
+  }
+  HIPCHK(hipGetLastError());
+  h->mark(3);
+  mp.total = 0;
+  int32_t over = 0, fcode = 0;
+  HIPCHK(hipMemcpyAsync(&mp.total, ecount, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&over, eover, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&fcode, gs->dfail, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  SgGeo ng;
+  const bool grow_pools = fcode == SG_ECAPACITY && !h->opt.no_grow && grown_geo(d, gs->geo, ng);
+  const bool grow_emit = over && !fcode && !h->opt.no_grow && mp.cap < ((int64_t)1 << 31);
+  if ((grow_pools || grow_emit) && attempt < 8) {
+    if (pre_bytes) HIPCHK(hipMemcpyAsync(gs->arena, pre, pre_bytes, hipMemcpyDeviceToDevice, st));   // roll back
+    if (grow_pools) regeo(h, gs, ng);
+    if (grow_emit) mp.cap = std::min<int64_t>((int64_t)1 << 31, mp.cap * 4);
+    ++gs->grows;
+    return false;
+  }
+  if (fcode) throw SgError(fcode, fcode == SG_ECAPACITY
+                                      ? "per-key pool/list capacity exceeded (raise sg_options pool_* / list_cap)"
+                                      : "query shape hits a reference failure path (see DESIGN.md)");
+  if (over) throw SgError(SG_ECAPACITY, "match buffer overflow: push smaller batches");
+  return true;
 }
 
 static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
@@ -580,11 +712,7 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
   h->kend();
   h->mark(2);
   // ---- per-key machines
-  int32_t stride = sg_emit_stride(d.n_select);
-  int64_t cap = n + 65536;
-  char* ebuf = nullptr;
-  unsigned long long* ecount = (unsigned long long*)h->ws.get("g_ecount", 16, st);
-  int32_t* eover = (int32_t*)h->ws.get("g_eover", 4, st);
+  const int32_t stride = sg_emit_stride(d.n_select);
   int32_t oerr = 0;
   int64_t tfl[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(&oerr, order_err, 4, hipMemcpyDeviceToHost, st));
@@ -630,132 +758,19 @@ static void run_machine(SgHandle* h, const BatchView& bv, int64_t n) {
     next_clock = std::max(gs->clock, last);
   }
   // ---- predicate-evaluation pass: condition bits of every state whose filter reads only the arriving event
-  for (int s = 0; s < SG_MAX_STATES; ++s) na.lbits[s] = nullptr;
-  {
-    const int64_t ntiles = (n + 255) / 256;
-    bool any = false;
-    for (int s = 0; s < d.n_states; ++s) {
-      const sg_state_desc& x = d.states[s];
-      if (!x.local || x.prog_len <= 0) continue;
-      if (!any) h->kbeg("pred");
-      any = true;
-      PredArgs pa;
-      memset(&pa, 0, sizeof(pa));
-      pa.n = n;
-      pa.stream = bv.stream;
-      pa.s_a = x.stream;
-      pa.prog_a_off = x.prog_off;
-      pa.prog_a_len = x.prog_len;
-      pa.val_col_a = -1;
-      pa.val_col_b = -1;
-      pa.cons_all = 1;
-      uint64_t* bits = (uint64_t*)h->ws.get("g_lbits" + std::to_string(s), sizeof(uint64_t) * 4 * (ntiles + 1), st);
-      launch_pred(d, pa, bv.stream, bv.cols, h->ddesc, bits, nullptr, st);
-      HIPCHK(hipGetLastError());
-      na.lbits[s] = bits;
-    }
-    if (any) h->kend();
-  }
+  local_pred_pass(h, bv, n, "g_lbits", na.lbits);
   // The reference's lists are unbounded (StreamPreStateProcessor.java:58-59): a push that runs out of a key's pool,
   // list or timer capacity, or out of emission space, is rolled back and rerun with 4x the capacity.
-  unsigned long long total = 0;
-  for (int attempt = 0;; ++attempt) {
-  const size_t pre_bytes = (size_t)kb * (size_t)gs->geo.key_words * 4;
-  int32_t* pre = (int32_t*)h->ws.get("g_pre", std::max<size_t>(pre_bytes, 4), st);
-  if (pre_bytes) HIPCHK(hipMemcpyAsync(pre, gs->arena, pre_bytes, hipMemcpyDeviceToDevice, st));
-  ebuf = (char*)h->ws.get("g_emit", (size_t)cap * stride, st);
-  HIPCHK(hipMemsetAsync(ecount, 0, 8, st));
-  HIPCHK(hipMemsetAsync(eover, 0, 4, st));
-  HIPCHK(hipMemsetAsync(gs->dfail, 0, 4, st));
-  SgEmitSink sink;
-  sink.buf = ebuf;
-  sink.cap = cap;
-  sink.count = ecount;
-  sink.overflow = eover;
-  sink.stride = stride;
-  sink.key_bits = kbits;
-  // ---- unit plan: one unit per key, or (chunkable shapes) per (key, chunk of R rows)
-  uint32_t R = 0;
-  // A time-horizon unit's runtime is rebuilt from the rows inside `within` before its chunk, so it lacks the partials
-  // parked in a count state since before that horizon: they never expire (CountPreStateProcessor.processAndReturn,
-  // C/query/input/stream/state/CountPreStateProcessor.java:53-93) and a later push whose time goes back can complete
-  // them -- queries with a count state are cut only by the sequence's event horizon
-  const bool count_q = has_count_state(d);
-  if (rule.kind != 0 && (rule.kind == 2 || (ts_monotone && !count_q)) && h->opt.chunk_rows >= 0 && n > 0) {
-    if (h->opt.chunk_rows > 0) {
-      R = (uint32_t)h->opt.chunk_rows;
-    } else {
-      // horizon rows per unit (rows of an average key inside `within`, or the sequence's event horizon);
-      // units at least 4x their horizon, enough of them to fill the chip, scratch arenas within budget
-      const int64_t span = std::max<int64_t>(1, tfl[1] - tfl[0]);
-      const double per_key = (double)n / (double)std::max<uint32_t>(kb, 1);
-      const double hz = rule.kind == 2 ? (double)rule.events : per_key * (double)rule.within / (double)span;
-      // (measured on C3b/C3c: 131k -> 524k units took 372 -> 245 ms and 3150 -> 2347 ms per 100M events;
-      // 1M units gained nothing more)
-      const int64_t target_units = 256 * 32 * 64;
-      const int64_t mem_units = std::max<int64_t>(1, ((int64_t)24 << 30) / ((int64_t)gs->geo.key_words * 4));
-      int64_t r = std::max<int64_t>({(int64_t)(4.0 * hz) + 1, 32, (n + target_units - 1) / target_units,
-                                     (n + mem_units - 1) / mem_units});
-      R = (uint32_t)std::min<int64_t>(r, 1 << 30);
-      if ((double)R >= per_key * 2.0) R = 0;   // hardly any key would be cut
-    }
-  }
-  if (R > 0) {
-    uint32_t* nch = (uint32_t*)h->ws.get("g_nch", sizeof(uint32_t) * (kb + 1), st);
-    uint32_t* uoff = (uint32_t*)h->ws.get("g_uoff", sizeof(uint32_t) * (kb + 1), st);
-    hipLaunchKernelGGL(k_unit_count, dim3((unsigned)((kb + 1 + 255) / 256)), blk, 0, st, (int64_t)kb, beg, end, R, nch);
-    sg_exclusive_scan(h->ws, st, "g_uscan_tmp", nch, uoff, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
-    uint32_t U = sg_read_back(uoff + kb, st);
-    const size_t kw = (size_t)gs->geo.key_words;
-    UnitArgs ua;
-    ua.R = R;
-    ua.rule = rule;
-    ua.n_units = U;
-    ua.uoff = uoff;
-    uint32_t* umap = (uint32_t*)h->ws.get("g_umap", sizeof(uint32_t) * std::max<uint32_t>(U, 1), st);
-    ua.umap = umap;
-    ua.scratch = (int32_t*)h->ws.get("g_uarena", sizeof(int32_t) * kw * std::max<uint32_t>(U, 1), st);
-    int32_t* snap = (int32_t*)h->ws.get("g_snap", sizeof(int32_t) * kw * kb, st);
-    HIPCHK(hipMemcpyAsync(snap, gs->arena, sizeof(int32_t) * kw * kb, hipMemcpyDeviceToDevice, st));
-    ua.snap = snap;
-    hipLaunchKernelGGL(k_unit_map, dim3((unsigned)((kb + 255) / 256)), blk, 0, st, (int64_t)kb, uoff, umap);
-    h->kbeg("nfa_units");
-    if (U)
-      hipLaunchKernelGGL(k_nfa_units, dim3((unsigned)((U + 63) / 64)), dim3(64), 0, st, na, ua, bv.cols, h->ddesc,
-                         gs->dgeo, gs->arena, sink, gs->dfail);
-    h->kend();
-    hipLaunchKernelGGL(k_unit_keep, dim3((unsigned)std::min<uint32_t>(std::max<uint32_t>(kb, 1), 65535)), blk, 0, st,
-                       (int64_t)kb, uoff, ua.scratch, gs->dgeo, gs->arena);
-  } else {
-    h->kbeg("nfa_keys");
-    hipLaunchKernelGGL(k_nfa, dim3((unsigned)((kb + 63) / 64)), dim3(64), 0, st, na, bv.cols, h->ddesc, gs->dgeo,
-                       gs->arena, sink, gs->dfail);
-    h->kend();
-  }
-  HIPCHK(hipGetLastError());
-  h->mark(3);
-  total = 0;
-  int32_t over = 0, fcode = 0;
-  HIPCHK(hipMemcpyAsync(&total, ecount, 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&over, eover, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&fcode, gs->dfail, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  SgGeo ng;
-  const bool grow_pools = fcode == SG_ECAPACITY && !h->opt.no_grow && grown_geo(d, gs->geo, ng);
-  const bool grow_emit = over && !fcode && !h->opt.no_grow && cap < ((int64_t)1 << 31);
-  if ((grow_pools || grow_emit) && attempt < 8) {
-    if (pre_bytes) HIPCHK(hipMemcpyAsync(gs->arena, pre, pre_bytes, hipMemcpyDeviceToDevice, st));   // roll back
-    if (grow_pools) regeo(h, gs, ng);
-    if (grow_emit) cap = std::min<int64_t>((int64_t)1 << 31, cap * 4);
-    ++gs->grows;
-    continue;
-  }
-  if (fcode) throw SgError(fcode, fcode == SG_ECAPACITY
-                                      ? "per-key pool/list capacity exceeded (raise sg_options pool_* / list_cap)"
-                                      : "query shape hits a reference failure path (see DESIGN.md)");
-  if (over) throw SgError(SG_ECAPACITY, "match buffer overflow: push smaller batches");
-  break;
-  }
+  MachinePush mp;
+  mp.kb = kb;
+  mp.kbits = kbits;
+  mp.rule = rule;
+  mp.ts_monotone = ts_monotone;
+  mp.span = tfl[1] - tfl[0];
+  mp.cap = n + 65536;
+  for (int attempt = 0; !machine_attempt(h, gs, bv, na, mp, attempt); ++attempt) {}
+  const unsigned long long total = mp.total;
+  const char* ebuf = mp.ebuf;
   // ---- order matches by (trigger, timer-before-event, key) keeping per-key emission order
   if (total) {
     uint64_t* sk = (uint64_t*)h->ws.get("g_sk", 8 * total, st);

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include "sg_device.h"
 #include "sg_engine.h"
@@ -319,4 +320,37 @@ static void launch_pred(const sg_nfa_desc& d, const PredArgs& pa, const int32_t*
     else if (depth <= SG_VM_STACK) hipLaunchKernelGGL(k_pred<SG_VM_STACK>, grd, blk, 0, st, ga, cols, ddesc, cand_m, cons_m);
     else throw SgError(SG_EUNSUPPORTED, "predicate program deeper than the VM stack");
   }
+}
+
+// The general family's predicate pass (the per-key machine and both lane routes): condition bits of every state whose
+// filter reads only the arriving event, over the n batch rows.  lbits[s] = the state's mask (workspace `prefix` + s),
+// nullptr for every other state.  Timed as "pred" when any state has such a filter.
+static void local_pred_pass(SgHandle* h, const BatchView& bv, int64_t n, const std::string& prefix,
+                            const uint64_t* lbits[SG_MAX_STATES]) {
+  const sg_nfa_desc& d = h->desc;
+  hipStream_t st = h->stream;
+  const int64_t ntiles = (n + 255) / 256;
+  bool any = false;
+  for (int s = 0; s < SG_MAX_STATES; ++s) lbits[s] = nullptr;
+  for (int s = 0; s < d.n_states; ++s) {
+    const sg_state_desc& x = d.states[s];
+    if (!x.local || x.prog_len <= 0) continue;
+    if (!any) h->kbeg("pred");
+    any = true;
+    PredArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.n = n;
+    pa.stream = bv.stream;
+    pa.s_a = x.stream;
+    pa.prog_a_off = x.prog_off;
+    pa.prog_a_len = x.prog_len;
+    pa.val_col_a = -1;
+    pa.val_col_b = -1;
+    pa.cons_all = 1;
+    uint64_t* bits = (uint64_t*)h->ws.get(prefix + std::to_string(s), sizeof(uint64_t) * 4 * (ntiles + 1), st);
+    launch_pred(d, pa, bv.stream, bv.cols, h->ddesc, bits, nullptr, st);
+    HIPCHK(hipGetLastError());
+    lbits[s] = bits;
+  }
+  if (any) h->kend();
 }

@@ -249,7 +249,8 @@ void sg_every_absent_reset(SgHandle* h);
 void sg_every_absent_release(SgHandle* h);
 void sg_general_reset(SgHandle* h);
 void sg_general_release(SgHandle* h);
-// partial-lane route of the general machine (partial.hip, chain.h)
+// lane routes of the general machine (partial.hip: the state, the push driver, snapshots; pp_rows.h, pp_lanes.h,
+// pp_emit.h: partial lanes over chain.h; sq_lanes.h: sequence lanes over seq.h)
 struct PartialState;
 PartialState* sg_partial_new(const sg_nfa_desc& d);   // nullptr: the query is outside the route (sg_pp_rule)
 void sg_partial_free(PartialState* ps);

@@ -21,12 +21,12 @@ struct HiHandle {
   std::vector<std::vector<char>> out;
   int err = 0;
   int chunk_rows = 0;   // >0: cut each key's rows into units replaying their horizon (as interp.hip does)
-  // partial lanes (chain.h, as partial.hip runs them): carried rows per push, values as retained-slot bits
+  // partial lanes (chain.h, as pp_lanes.h runs them): carried rows per push, values as retained-slot bits
   int pp = 0;
   int pp_active = 1;
   struct CRow { int64_t ts; int32_t key; int64_t vals[SG_MAX_RET]; int32_t nullmask; uint8_t start; };
   std::vector<CRow> carried;
-  std::vector<SeqState> seq_state;   // sequence lanes: per key (partial.hip's geometry choice: big ...)
+  std::vector<SeqState> seq_state;   // sequence lanes: per key (partial.hip's geometry choice in sg_partial_new: big ...)
   std::vector<SeqStateT<SqSmall>> seq_state_s;   // (... or small, sg_seq_small)
   int64_t spec_rows = 0, spec_warm = 0, spec_reruns = 0;   // speculative units (0: one run per key)
   int64_t pp_steps = 0, pp_lanes = 0, pp_skipped = 0;      // partial lanes: rows stepped, lanes started, rows skipped
@@ -122,7 +122,7 @@ struct HostPpSrc {
   }
 };
 
-// partial-lane push (partial.hip restated on the host); returns -1 when a lane outgrows its arrays
+// partial-lane push (partial.hip sg_partial_push and its stages in pp_rows.h / pp_lanes.h restated on the host); returns -1 when a lane outgrows its arrays
 template <class G, class SH = PpShapeAny>
 static int pp_push(HiHandle* h, const sg_batch* b, std::vector<char>& recs, std::vector<uint64_t>& k1,
                    std::vector<uint64_t>& th, std::vector<uint64_t>& tl) {
@@ -249,7 +249,7 @@ static int pp_push(HiHandle* h, const sg_batch* b, std::vector<char>& recs, std:
   return 1;
 }
 
-// sequence-lane push (partial.hip's sequence route restated on the host): one compact machine per key, resumed from the
+// sequence-lane push (sq_lanes.h seq_lanes_push restated on the host): one compact machine per key, resumed from the
 // key's carried state over its carried rows (the last H) + this push's rows; returns 0 when the machine overflows
 struct HostSeqSrc {
   HostPpSrc base_src;
@@ -346,7 +346,7 @@ static int seq_push(HiHandle* h, std::vector<SeqStateT<G>>& states, const sg_bat
     if (R <= 0 || nk - ncar[k] <= R) {
       if (!run(ncar[k], nk, true)) return 0;
     } else {
-      // speculative units (partial.hip's scheme): unit c > 0 starts from a zeroed state warmed up over the W rows before
+      // speculative units (sq_lanes.h's scheme): unit c > 0 starts from a zeroed state warmed up over the W rows before
       // it; a unit whose warmed-up start differs from its predecessor's end is rerun from that end; then every unit
       // runs again from its verified start, emitting
       const int64_t U = (nk - ncar[k] + R - 1) / R;
@@ -445,7 +445,7 @@ int hi_push(HiHandle* h, const sg_batch* b) {
     const std::vector<SeqState> before_st = h->seq_state;
     const std::vector<SeqStateT<SqSmall>> before_s = h->seq_state_s;
     const bool small = sg_seq_small(sg_seq_rule(h->d), h->d);
-    // (partial.hip's kernel choice: the specialised machine for C3b's family in the small geometry)
+    // (sq_lanes.h seq_spec_fn's kernel choice: the specialised machine for C3b's family in the small geometry)
     const bool c3b = small && sg_sq_shape_is<SqShapeC3b>(h->d, sg_seq_rule(h->d));
     if (c3b ? seq_push<SqSmall, SqShapeC3b>(h, h->seq_state_s, b, recs, k1)
             : small ? seq_push(h, h->seq_state_s, b, recs, k1) : seq_push(h, h->seq_state, b, recs, k1)) {

@@ -77,7 +77,7 @@ def test_machine_without_growth_still_reports_capacity():
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("cap", [16, 3000])
 def test_sequence_lanes_regrow_match_space(monkeypatch, cap):
-    """Sequence lanes (C3b's route, csrc/partial.hip seq_lanes_push) start from a match space of `cap` slots
+    """Sequence lanes (C3b's route, csrc/sq_lanes.h seq_lanes_push) start from a match space of `cap` slots
     (SG_DEBUG_SQ_MATCH_CAP, a test hook): the first push and every later one outgrow it, and each is rerun from its unchanged
     start states with four times the space -- no push fails (the second push used to throw
     SG_ECAPACITY "match buffer").  Three pushes with carried state, oracle-equal."""
