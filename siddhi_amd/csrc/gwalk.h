@@ -22,6 +22,12 @@
 // arrival order gives each trigger's first output slot, and the projection walks the triggers in arrival order,
 // so the output records are written contiguously and in delivery order.
 //
+// Trigger words are not cleared per push.  A word is unit (32) | matches (24) | epoch (8); the epoch
+// is a per-handle counter in 1..255 that advances with every group-walked push, and a word of any other epoch reads
+// as "no trigger" -- what an earlier push, or a push the walker declined half way, left behind.  The buffer is
+// cleared only where it could hold untagged bytes (a new allocation, words past the high-water mark) and when the
+// epochs wrap (gw_tagged_words).
+//
 // The fast path declines (run_group_walk returns 0, nothing changed) when a push needs what only the tiled path has: a key
 // whose time goes back (the exact HBM-list walker), a pending list longer than the LDS ring, e1 attributes gathered
 // by row, or a select reading anything but the compared values and the carried payload.
@@ -52,7 +58,8 @@ struct GwArgs {
   const PtU4* grec;           // pass 1b's records, grouped by group, arrival order within a group
   const uint8_t* glk;         // in-group key of each record
   const uint32_t* kbase;      // per key: its first row in the group domain (exclusive scan of per-key rows)
-  uint64_t* trig;             // per batch row: match-area unit of its first header | matches << 32 (0: none)
+  uint64_t* trig;             // per batch row: gw_trig_word(match-area unit of its header, matches, epoch)
+  uint32_t epoch;             // this push's tag (1..255): a word tagged otherwise is no trigger
   uint64_t* area;             // match area, 8-byte units: 3 per row of the key
   int64_t* cv_ts;             // carry: every key's final pending list as values
   int32_t* cv_key;
@@ -67,6 +74,17 @@ struct GwArgs {
   uint32_t* match_n;          // matches of the push (the projection's output size)
 };
 static const uint32_t GW_ORDER = 1, GW_OVERFLOW = 2, GW_INTERNAL = 4, GW_CARRY_FULL = 8;
+
+// Trigger word: unit (32) | matches (24) | epoch (8).  The buffer is not cleared per push: a word counts only when
+// its epoch is the push's (run_group_walk hands the epochs out and clears what could hold anything else).
+static const uint32_t GW_MATCH_MAX = (1u << 24) - 1;
+__device__ __forceinline__ uint64_t gw_trig_word(uint64_t unit, uint32_t m, uint32_t epoch) {
+  return unit | ((uint64_t)m << 32) | ((uint64_t)epoch << 56);
+}
+// matches of a trigger word under `epoch` (0: the row triggered nothing in this push)
+__device__ __forceinline__ uint32_t gw_trig_matches(uint64_t w, uint32_t epoch) {
+  return (uint32_t)(w >> 56) == epoch ? (uint32_t)(w >> 32) & GW_MATCH_MAX : 0u;
+}
 
 // per-key rows of every group (LDS counters over the group's in-group keys)
 static __global__ void __launch_bounds__(256) k_gw_count(const uint32_t* __restrict__ o1, uint32_t ns1, uint32_t K,
@@ -119,6 +137,7 @@ struct GwLane {
   int32_t hts = 0, prev = INT32_MIN;
   T tv = T();
   bool bad = false;
+  bool big = false;   // a trigger completed more partials than a trigger word counts (an unbounded list only)
   uint64_t cur = 0;   // next free unit of the key's match-area region
   uint32_t k = 0;
   uint32_t nm = 0;    // matches delivered
@@ -198,7 +217,8 @@ struct GwLane {
         const uint64_t b = r - (uint32_t)a.nc;
         a.area[hdr] = (uint64_t)(uint32_t)dts | ((uint64_t)k << 32);
         a.area[hdr + 1] = (uint64_t)(uint32_t)val_bits<T>(x) | ((uint64_t)(uint32_t)pay << 32);
-        a.trig[b] = hdr | ((uint64_t)m << 32);
+        big |= m > GW_MATCH_MAX;
+        a.trig[b] = gw_trig_word(hdr, m & GW_MATCH_MAX, a.epoch);
         cur = hdr + 2 + m;
         nm += m;
       }
@@ -352,8 +372,8 @@ __global__ void __launch_bounds__(256, 1) k_gwalk(GwArgs a) {
 // workgroup per such key gathers the key's rows from its group (arrival order kept) into the key's slice of `rows`,
 // then one lane walks them (staged in LDS with the list when the key has at most GW_REDO_LDS rows, else from HBM with
 // the list in HBM planes over the key's rows), rewriting the key's match-area region,
-// its trigger words and its carry from the start (same walk, same rows: the same words the first walk wrote up to
-// the overflow, then the rest).
+// its trigger words (under the push's epoch, as the first walk tagged them) and its carry from the start (same walk,
+// same rows: the same words the first walk wrote up to the overflow, then the rest).
 static const uint32_t GW_REDO_LDS = 2048;   // rows of a redone key walked from LDS
 template <class T, int OP, bool STACK>
 __global__ void __launch_bounds__(256) k_gw_redo(GwArgs a, uint32_t* __restrict__ rows, T* __restrict__ hv,
@@ -406,6 +426,7 @@ __global__ void __launch_bounds__(256) k_gw_redo(GwArgs a, uint32_t* __restrict_
   else for (uint32_t i = kb; i < ke; ++i) W.step(a, a.grec[rows[i]]);
   uint32_t fl = W.bad ? GW_ORDER : 0u;
   if (W.cur > 3ull * ke) fl |= GW_INTERNAL;
+  if (W.big) fl |= GW_OVERFLOW;   // 2^24 or more matches of one trigger: the tiled path (the LDS ring holds 32)
   if (fl) atomicOr(a.flags, fl);
   if (W.nm) atomicAdd(a.match_n, W.nm);
   if (!a.carry_out) return;
@@ -422,21 +443,24 @@ __global__ void __launch_bounds__(256) k_gw_redo(GwArgs a, uint32_t* __restrict_
 // stores by consecutive threads); a block whose rows deliver more than GW_PROJ_S records does it in rounds.
 struct GwSel {
   int32_t n_select, stride, multi, b_slot, pzero, vfloat;
-  int32_t code[SG_MAX_SELECT];   // 0 e1 payload, 1 e1 value, 2 e2 value, 3 e2 payload, 4 null
+  uint32_t nmask;      // null-mask bits of the record: the columns of code 4
+  uint32_t pad;
+  uint64_t codes[2];   // 4 bits per select column: 0 e1 payload, 1 e1 value, 2 e2 value, 3 e2 payload, 4 null
 };
+static_assert(SG_MAX_SELECT <= 32, "GwSel packs 32 select codes");
 static const int GW_PROJ_S = 256;   // records staged per round
 static const int GW_TILE = 256;     // rows per projection tile (one per thread)
 
 // matches per 256-row tile of trigger words, eight tiles per workgroup (the projection's tile bases come from a scan
 // over these)
-static __global__ void __launch_bounds__(256) k_gtile_count(int64_t n, const uint64_t* __restrict__ trig,
+static __global__ void __launch_bounds__(256) k_gtile_count(int64_t n, const uint64_t* __restrict__ trig, uint32_t epoch,
                                                             uint32_t* __restrict__ tcount, int64_t ntile) {
   __shared__ uint32_t red[8][4];
   const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63;
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const int64_t r = ((int64_t)blockIdx.x * 8 + s) * GW_TILE + t;
-    uint32_t c = r < n ? (uint32_t)(__builtin_nontemporal_load(trig + r) >> 32) : 0u;
+    uint32_t c = r < n ? gw_trig_matches(__builtin_nontemporal_load(trig + r), epoch) : 0u;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
     if (lane == 0) red[s][w] = c;
@@ -453,7 +477,7 @@ static __global__ void __launch_bounds__(256) k_gtile_count(int64_t n, const uin
 // assembled in LDS in slot order and stored contiguously (GW_PROJ_S records per round).
 static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t t0, uint64_t base_index,
                                                               const uint64_t* __restrict__ index,
-                                                              const uint64_t* __restrict__ trig,
+                                                              const uint64_t* __restrict__ trig, uint32_t epoch,
                                                               const uint64_t* __restrict__ area, GwSel sel,
                                                               int64_t out_base, char* __restrict__ out,
                                                               const uint32_t* __restrict__ tbase) {
@@ -462,7 +486,7 @@ static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t
   const uint32_t t = threadIdx.x;
   const int64_t b = (int64_t)blockIdx.x * GW_TILE + t;
   const uint64_t tw = b < n ? __builtin_nontemporal_load(trig + b) : 0ull;
-  const uint32_t m = (uint32_t)(tw >> 32);
+  const uint32_t m = gw_trig_matches(tw, epoch);
   const uint64_t u = (uint32_t)tw;
   uint64_t h0 = 0, h1 = 0, tg = 0;
   if (m) {
@@ -475,8 +499,10 @@ static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t
   const uint32_t o_lo = pre, o_hi = pre + (wsum[0] + wsum[1] + wsum[2] + wsum[3]);
   const uint32_t o = pre + excl;
   auto wid = [&](uint32_t bits, bool zero) { return zero ? (int64_t)bits : (int64_t)(int32_t)bits; };
-  uint32_t nmask = 0;
-  for (int s = 0; s < sel.n_select; ++s) nmask |= (sel.code[s] == 4) ? 1u << s : 0u;
+  // (the select codes and the null mask come packed in registers: nothing is read from the arguments per match)
+  const uint64_t cw0 = sel.codes[0], cw1 = sel.codes[1];
+  const int nsel = sel.n_select;
+  const int64_t nmask = (int64_t)sel.nmask;
   const int64_t ts = t0 + (int64_t)(int32_t)(uint32_t)h0;
   const uint32_t key = (uint32_t)(h0 >> 32);
   const int64_t v2 = wid((uint32_t)h1, sel.vfloat), p2 = wid((uint32_t)(h1 >> 32), sel.pzero);
@@ -492,9 +518,9 @@ static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t
         r[0] = (int64_t)tg;
         r[1] = ts;
         r[2] = (int64_t)((uint64_t)key | ((uint64_t)((1u << 24) | (sel.multi ? (uint32_t)sel.b_slot : (0x800000u | q))) << 32));
-        r[3] = (int64_t)nmask;
-        for (int c = 0; c < sel.n_select; ++c) {
-          const int code = sel.code[c];
+        r[3] = nmask;
+        for (int c = 0; c < nsel; ++c) {
+          const uint32_t code = (uint32_t)((c < 16 ? cw0 >> (4 * c) : cw1 >> (4 * (c - 16))) & 15u);
           r[4 + c] = code == 0 ? p1 : code == 1 ? v1 : code == 2 ? v2 : code == 3 ? p2 : 0;
         }
       }
@@ -540,7 +566,8 @@ static GwPlan gw_plan(SgHandle* h, const BatchView& bv, int64_t n, int64_t nc, u
     else if (kind == 1) code = src ? 2 : 1;
     else if (kind == 3 && src == 1 && plan.pcol >= 0 && plan.pp.col[s] == plan.pcol) code = 3;
     if (code < 0) return g;
-    g.sel.code[s] = code;
+    g.sel.codes[s >> 4] |= (uint64_t)code << (4 * (s & 15));
+    if (code == 4) g.sel.nmask |= 1u << s;
   }
   const int64_t win = window_rows(kb, nc + n, d.within, span_ms);
   // the ring as the tiled walker sizes it (a key whose list outgrows it is walked again on an unbounded list by
@@ -586,6 +613,27 @@ static void launch_gwalk(const GwArgs& ga, uint32_t ng, hipStream_t st) {
   }
 }
 
+// Words of a named workspace that are tagged with the push's epoch instead of being cleared per push: clears what
+// could hold anything but zero or a word tagged since the last clear -- everything after the workspace was allocated
+// anew (ws.get never zeroes), the words past the high-water mark of the pushes so far, and, when the epochs wrap
+// (`wrap`: this push starts them again at 1), the words used so far.
+static uint64_t* gw_tagged_words(SgHandle* h, SgHandle::GwTagged& tw, const char* name, size_t words, bool wrap,
+                                 hipStream_t st) {
+  uint64_t* p = (uint64_t*)h->ws.get(name, sizeof(uint64_t) * words, st);
+  const size_t cap = h->ws.bufs[name].bytes;
+  if (p != tw.p || cap != tw.cap) {
+    tw.p = p;
+    tw.cap = cap;
+    tw.hw = 0;
+  }
+  if (wrap && tw.hw) HIPCHK(hipMemsetAsync(p, 0, sizeof(uint64_t) * tw.hw, st));
+  if (words > tw.hw) {
+    HIPCHK(hipMemsetAsync(p + tw.hw, 0, sizeof(uint64_t) * (words - tw.hw), st));
+    tw.hw = words;
+  }
+  return p;
+}
+
 // the delivered matches of a group-walked push -> output records: per-tile match counts -> tile bases (scan) ->
 // output records per tile (block scan inside the tile)
 static void gw_project(SgHandle* h, const BatchView& bv, int64_t n, const GwArgs& ga, const GwSel& sel, uint32_t total) {
@@ -597,8 +645,8 @@ static void gw_project(SgHandle* h, const BatchView& bv, int64_t n, const GwArgs
   uint32_t* tbase = (uint32_t*)h->ws.get("gw_tbase", sizeof(uint32_t) * ((size_t)ntile + 1), st);
   h->kbeg("gw_tiles");
   HIPCHK(hipMemsetAsync(tcount + ntile, 0, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_gtile_count, dim3((unsigned)((ntile + 7) / 8)), dim3(256), 0, st, n, (const uint64_t*)ga.trig, tcount,
-                     ntile);
+  hipLaunchKernelGGL(k_gtile_count, dim3((unsigned)((ntile + 7) / 8)), dim3(256), 0, st, n, (const uint64_t*)ga.trig, ga.epoch,
+                     tcount, ntile);
   HIPCHK(hipGetLastError());
   sg_exclusive_scan(h->ws, st, "gw_tscan_tmp", tcount, tbase, (uint32_t)0, (size_t)ntile + 1, rocprim::plus<uint32_t>());
   h->kend();
@@ -609,7 +657,7 @@ static void gw_project(SgHandle* h, const BatchView& bv, int64_t n, const GwArgs
   if (plds > 65536)
     HIPCHK(hipFuncSetAttribute((const void*)k_gscan_project, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
   hipLaunchKernelGGL(k_gscan_project, dim3((unsigned)ntile), dim3(256), plds, st, n, ga.t0, bv.base_index, bv.index,
-                     (const uint64_t*)ga.trig, (const uint64_t*)ga.area, sel, (int64_t)h->out.n, out,
+                     (const uint64_t*)ga.trig, ga.epoch, (const uint64_t*)ga.area, sel, (int64_t)h->out.n, out,
                      (const uint32_t*)tbase);
   HIPCHK(hipGetLastError());
   h->kend();
@@ -668,7 +716,13 @@ static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t n
   ga.grec = (const PtU4*)grec;
   ga.glk = glk;
   ga.kbase = kbase;
-  ga.trig = (uint64_t*)h->ws.get("gw_trig", sizeof(uint64_t) * ((size_t)n + 1), st);
+  // this push's epoch, and the words it tags: nothing is cleared in steady state (gw_tagged_words)
+  const char* ee = getenv("SG_DEBUG_GW_EPOCHS");   // (test hook: wrap after that many epochs)
+  const uint32_t epochs = ee ? (uint32_t)std::min(std::max(atoi(ee), 1), 255) : 255u;
+  const bool wrap = h->gw_epoch >= epochs;
+  h->gw_epoch = wrap ? 1u : h->gw_epoch + 1;
+  ga.epoch = h->gw_epoch;
+  ga.trig = gw_tagged_words(h, h->gw_trig, "gw_trig", (size_t)std::max<int64_t>(n, 1), wrap, st);
   ga.area = (uint64_t*)h->ws.get("gw_area", sizeof(uint64_t) * 3 * (size_t)std::max<int64_t>(nt, 1), st);
   uint32_t* gflags = (uint32_t*)h->ws.get("gw_flags", sizeof(uint32_t) * 4, st);
   ga.flags = gflags;
@@ -685,7 +739,6 @@ static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t n
   ga.cv_pay = (int64_t*)h->ws.get("cv_pay", sizeof(int64_t) * (size_t)ga.cv_cap, st);
   ga.cv_key = (int32_t*)h->ws.get("cv_key", sizeof(int32_t) * (size_t)ga.cv_cap, st);
   HIPCHK(hipMemsetAsync(gflags, 0, sizeof(uint32_t) * 4, st));
-  HIPCHK(hipMemsetAsync(ga.trig, 0, sizeof(uint64_t) * ((size_t)n + 1), st));
   h->kbeg("group_walk");
   dispatch_op(op, [&](auto opc) { launch_gwalk<T, decltype(opc)::value>(ga, ng, st); });
   h->kend();

@@ -128,6 +128,11 @@ struct SgHandle {
   uint64_t snap_gen = ~0ull;
   uint32_t key_bound_seen = 0;
   int64_t ts_max_seen = INT64_MIN;   // largest timestamp pushed so far (sg_options.bounded_lateness)
+  // group walker (gwalk.h): device words tagged with a per-push epoch in place of a zero fill per push.  `hw` words
+  // from the start of the allocation (p, cap) hold zero or a word tagged by an epoch handed out since the last clear.
+  struct GwTagged { const void* p = nullptr; size_t cap = 0, hw = 0; };
+  GwTagged gw_trig;             // the trigger words (one per batch row)
+  uint32_t gw_epoch = 0;        // epoch of the last group-walked push (1..255; 0: none yet)
   void* state = nullptr;      // per-shape persistent state (interp / absent)
   int state_kind = 0;         // 1 every->next closed form, 2 general machine, 3 absence closed form, 4 once closed form
   int split_out = 0;          // 1: output stage timed from ev[5] (host work between ev[3] and ev[5])
