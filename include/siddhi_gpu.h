@@ -309,6 +309,42 @@ int sg_router_dense_ids(const sg_router* r, int32_t shard, int32_t* dense_of_loc
 int sg_merge_order(int n_runs, const int64_t* run_len, const uint64_t* const* trigger, const uint32_t* const* group,
                    const int32_t* const* key, int threads, int64_t* out_src);
 
+/* ---- Device range router (ranges.hip): PartitionStreamReceiver with RangePartitionExecutors
+ * (C/partition/PartitionStreamReceiver.java:94-100,110-125,270-275; C/partition/executor/RangePartitionExecutor.java:
+ * 38-43) for SoA batches, on the GPU.  A row of a range-partitioned stream becomes one copy per range whose condition
+ * holds, in the written range order, each copy with the row's event index and the dense key of the range's label; a
+ * row that holds no range is dropped (playback: kept as one clock-only row, stream -1 and key -1); rows of every
+ * other stream (stream -1 included) pass through with their in->key.  The routed batch is ready for sg_push.
+ * The router owns no key ids: label_key[l] is the caller's dense key of label code l (-1 = not assigned yet); labels
+ * first held in this batch receive *next_key, *next_key + 1, ... in first-seen order over the copies (increasing
+ * (row, range position)), label_key is updated in place and *next_key advanced. */
+#define SG_MAX_RANGES 32
+typedef struct sg_range_desc {
+  int32_t abi_version, playback;        /* playback 1: a row of a range stream that holds no range stays as ONE clock-only row */
+  int32_t n_cols, col_type[SG_MAX_COLS], col_stream[SG_MAX_COLS];   /* as in sg_nfa_desc */
+  int32_t n_ranges, n_labels;           /* every range stream's ranges, written order within a stream */
+  int32_t range_stream[SG_MAX_RANGES], range_label[SG_MAX_RANGES];  /* label code: ranges with the same label string share one */
+  int32_t prog_off[SG_MAX_RANGES], prog_len[SG_MAX_RANGES];
+  int32_t code_len; int64_t code[SG_MAX_CODE];   /* the existing postfix opcodes; SG_OP_VAR word 3 = batch column */
+} sg_range_desc;
+typedef struct sg_range_stats {
+  int64_t rows, copies, calls;          /* since sg_range_open: input rows, routed rows (out->n), sg_range_route calls */
+  float hold_ms, expand_ms;             /* HIP-event times of the last call's hold and expand kernels */
+} sg_range_stats;
+typedef struct sg_range_router sg_range_router;
+/* SG_EINVAL for a bad descriptor, SG_EUNSUPPORTED for a program deeper than the VM stack; on failure *out still
+ * receives a router that only sg_range_last_error and sg_range_close accept. */
+int sg_range_open(int hip_device, const sg_range_desc* d, sg_range_router** out);
+/* `in`: a host batch (columns copied up first) or a device batch (read in place); in->key_bound must be set whenever a
+ * row carries a key >= 0.  `out`: a device batch (on_device = 1) in buffers the router owns, complete when the call
+ * returns and valid until the next sg_range_route / sg_range_close (sg_flush the handle it was pushed to first);
+ * out->cols[c] / out->nulls[c] are NULL where in's are, out->index is always filled,
+ * out->key_bound = max(in->key_bound, 1 + the largest label key). */
+int sg_range_route(sg_range_router* r, const sg_batch* in, int32_t* label_key, int32_t* next_key, sg_batch* out);
+int sg_range_stats_get(const sg_range_router* r, sg_range_stats* st);
+int sg_range_close(sg_range_router* r);
+const char* sg_range_last_error(const sg_range_router* r);
+
 /* ---- Node pipeline: one host process drives the node's GPUs for one partitioned query ----------------------------
  * Replaces PartitionStreamReceiver.receive(Event[]) (C/partition/PartitionStreamReceiver.java:177-221) feeding the
  * per-key cloned runtimes (C/partition/PartitionRuntime.java:255-308) and the ordered delivery to QueryCallback

@@ -15,13 +15,15 @@ LIB_PATH = os.environ.get("SIDDHI_GPU_LIB") or os.path.join(HERE, "libsiddhi_gpu
 
 SG_MAX_STATES, SG_MAX_STREAMS, SG_MAX_SELECT, SG_MAX_RET, SG_MAX_COLS, SG_MAX_CODE = 16, 16, 32, 16, 64, 512
 SG_ABI_VERSION = 4
+SG_EUNSUPPORTED = -4
 
 SYMBOLS = ["sg_open", "sg_push", "sg_advance_time", "sg_pending", "sg_poll", "sg_device_records", "sg_discard",
            "sg_flush", "sg_reset", "sg_set_stream", "sg_get_timing", "sg_close", "sg_last_error", "sg_version",
            "sg_snapshot", "sg_restore", "sg_host_alloc", "sg_host_free", "sg_poll_columns", "sg_push_deliver",
            "sg_router_open", "sg_router_route", "sg_router_keys", "sg_router_close", "sg_router_dense_ids",
            "sg_merge_order", "sg_node_open", "sg_node_push", "sg_node_reset", "sg_node_stats_get", "sg_node_keys",
-           "sg_node_close", "sg_node_last_error", "sg_node_set_key_dict"]
+           "sg_node_close", "sg_node_last_error", "sg_node_set_key_dict", "sg_range_open", "sg_range_route",
+           "sg_range_stats_get", "sg_range_close", "sg_range_last_error"]
 
 I32, I64, U64 = ct.c_int32, ct.c_int64, ct.c_uint64
 
@@ -99,6 +101,21 @@ class sg_node_stats(ct.Structure):
 
 class sg_match_records(ct.Structure):
     _fields_ = [("n", I64), ("record_bytes", I32), ("n_select", I32), ("base", ct.c_void_p)]
+
+
+SG_MAX_RANGES = 32
+
+
+class sg_range_desc(ct.Structure):
+    _fields_ = [("abi_version", I32), ("playback", I32), ("n_cols", I32), ("col_type", I32 * SG_MAX_COLS),
+                ("col_stream", I32 * SG_MAX_COLS), ("n_ranges", I32), ("n_labels", I32),
+                ("range_stream", I32 * SG_MAX_RANGES), ("range_label", I32 * SG_MAX_RANGES),
+                ("prog_off", I32 * SG_MAX_RANGES), ("prog_len", I32 * SG_MAX_RANGES),
+                ("code_len", I32), ("code", I64 * SG_MAX_CODE)]
+
+
+class sg_range_stats(ct.Structure):
+    _fields_ = [("rows", I64), ("copies", I64), ("calls", I64), ("hold_ms", ct.c_float), ("expand_ms", ct.c_float)]
 
 
 SG_MAX_KMARKS = 24
@@ -185,6 +202,12 @@ def load_library(path: str = LIB_PATH):
         lib.sg_node_set_key_dict.argtypes = [P, ct.c_int]
         lib.sg_node_last_error.argtypes = [P]
         lib.sg_node_last_error.restype = ct.c_char_p
+        lib.sg_range_open.argtypes = [ct.c_int, P, ct.POINTER(P)]
+        lib.sg_range_route.argtypes = [P, P, P, ct.POINTER(I32), P]
+        lib.sg_range_stats_get.argtypes = [P, P]
+        lib.sg_range_close.argtypes = [P]
+        lib.sg_range_last_error.argtypes = [P]
+        lib.sg_range_last_error.restype = ct.c_char_p
         lib.sg_last_error.argtypes = [P]
         lib.sg_last_error.restype = ct.c_char_p
         lib.sg_version.restype = ct.c_char_p
@@ -452,6 +475,72 @@ class Router:
             pass
 
 
+def build_range_desc(rt: L.RangeTable) -> sg_range_desc:
+    d = sg_range_desc()
+    d.abi_version = SG_ABI_VERSION
+    d.playback = rt.playback
+    d.n_cols = len(rt.cols)
+    for c, (s, _, t) in enumerate(rt.cols):
+        d.col_type[c] = L.TYPE_CODE[t]
+        d.col_stream[c] = s
+    d.n_ranges = len(rt.ranges)
+    d.n_labels = len(rt.labels)
+    code = []
+    for k, (s, label, prog) in enumerate(rt.ranges):
+        d.range_stream[k], d.range_label[k] = s, label
+        d.prog_off[k], d.prog_len[k] = len(code), len(prog)
+        code += prog
+    d.code_len = len(code)
+    for k, w in enumerate(code):
+        d.code[k] = int(w)
+    return d
+
+
+class RangeRouter:
+    """The device range router (sg_range_*): a batch's rows of range-partitioned streams become one copy per holding
+    range, in HBM, ready for sg_push.  Raises SgError (code SG_EUNSUPPORTED for programs the VM cannot hold)."""
+
+    def __init__(self, desc: sg_range_desc, device: int = 0):
+        self._pid = os.getpid()
+        self.lib = load_library()
+        self.r = ct.c_void_p()
+        self.desc = desc
+        rc = self.lib.sg_range_open(device, ct.byref(desc), ct.byref(self.r))
+        if rc != 0:
+            msg = self.lib.sg_range_last_error(self.r).decode() if self.r else ""
+            self.close()
+            raise SgError(rc, msg)
+
+    def route(self, b: sg_batch, label_key: np.ndarray, next_key: int):
+        """sg_range_route: (routed device sg_batch, new next_key); label_key (int32[n_labels]) is updated in place.
+        The routed batch lives in the router's buffers until the next route or close."""
+        assert label_key.dtype == np.int32 and label_key.flags.c_contiguous and len(label_key) >= self.desc.n_labels
+        out = sg_batch()
+        nk = I32(int(next_key))
+        rc = self.lib.sg_range_route(self.r, ct.byref(b), label_key.ctypes.data, ct.byref(nk), ct.byref(out))
+        if rc != 0:
+            raise SgError(rc, self.lib.sg_range_last_error(self.r).decode())
+        return out, nk.value
+
+    def stats(self) -> sg_range_stats:
+        st = sg_range_stats()
+        self.lib.sg_range_stats_get(self.r, ct.byref(st))
+        return st
+
+    def close(self):
+        if self.r:
+            self.lib.sg_range_close(self.r)
+            self.r = None
+
+    def __del__(self):
+        if getattr(self, "_pid", os.getpid()) != os.getpid():
+            return   # (a forked child's copy: the parent owns the native object)
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def merge_order(triggers, groups=None, keys=None, threads: int = 16) -> np.ndarray:
     """sg_merge_order: the node's delivery order of several match runs (each in delivery order) as indices into
     their concatenation -- by (trigger, phase, dense key), ties in run order."""
@@ -603,10 +692,38 @@ class GpuEngine:
             opts.pool_partials = opts.pool_events = opts.pool_chain = opts.list_cap = pool
         self.handle = Handle(self.desc, device, opts)
         self.nsel = len(self.nfa.out_progs) or len(self.nfa.select)
+        # range-partitioned streams: the device router, unless its limits refuse the query (the runtime then keeps
+        # routing on the host)
+        self.range_router = None
+        self.range_labels = []
+        try:
+            table = L.lower_ranges(ctx)
+            if table is not None:
+                self.range_router = RangeRouter(build_range_desc(table), device)
+                self.range_labels = list(table.labels)
+        except L.LoweringError:
+            pass
+        except SgError as e:
+            if e.code != SG_EUNSUPPORTED:
+                raise
 
     def push(self, b):
-        import numpy as np
         keep = []
+        self.handle.push(self._host_batch(b, keep))
+
+    def push_ranges(self, b, label_key, next_key: int) -> int:
+        """Route b's rows of range-partitioned streams on the device (sg_range_route) and push the routed batch.
+        label_key: int32 dense key per label code of range_labels (-1: unassigned), updated in place; returns the
+        next free key after the labels first held in this batch took theirs."""
+        keep = []
+        routed, next_key = self.range_router.route(self._host_batch(b, keep), label_key, next_key)
+        if routed.n:
+            self.handle.push(routed)
+            self.handle.flush()    # the routed rows live in the router's buffers: done with them before the next route
+        return next_key
+
+    def _host_batch(self, b, keep) -> sg_batch:
+        """b (runtime.Batch) as a host sg_batch; `keep` receives the arrays it points into"""
         ts = np.ascontiguousarray(b.ts, np.int64)
         st = None if b.stream is None else np.ascontiguousarray(b.stream, np.int32)   # None: every row stream 0
         ky = np.ascontiguousarray(b.key, np.int32)
@@ -621,7 +738,7 @@ class GpuEngine:
         sb = make_batch(b.n, b.base_index, ts.ctypes.data, 0 if st is None else st.ctypes.data, ky.ctypes.data,
                         [c.ctypes.data for c in cols], [(x.ctypes.data if x is not None else 0) for x in b.nulls],
                         0, kb, keep, index=ix)
-        self.handle.push(sb)
+        return sb
 
     def fetch(self):
         from .runtime import Outputs
@@ -638,4 +755,6 @@ class GpuEngine:
         self.handle.restore(blob)
 
     def close(self):
+        if self.range_router is not None:
+            self.range_router.close()
         self.handle.close()

@@ -790,3 +790,61 @@ def _classify(nfa: FlatNFA, root, b: _FlatBuilder):
 
 def lower(ctx: QueryContext) -> FlatNFA:
     return _FlatBuilder(ctx).build()
+
+
+# ==============================================================================================
+# Range partitions for the device router (sg_range_desc)
+# ==============================================================================================
+MAX_RANGES = 32
+
+
+@dataclass
+class RangeTable:
+    """The content of an sg_range_desc: every range stream's ranges (streams by index, written order within a
+    stream), one label code per distinct label string across streams, one postfix program per condition."""
+    playback: int
+    cols: List[Tuple[int, int, str]]
+    labels: List[str]                              # label code -> label string
+    ranges: List[Tuple[int, int, list]]            # (stream index, label code, program)
+
+
+def _range_prog(ctx: QueryContext, s: int, e) -> Tuple[list, str]:
+    """Postfix program of a range condition over the batch columns of stream s, by the rules of compile_expr (a VAR's
+    word 3 is the batch column; the conditions are those _check_range_cond accepts)."""
+    if isinstance(e, C.Const):
+        img = _enc_const(ctx, e)
+        return [OP_CONST, img[1], img[2]], e.type
+    if isinstance(e, C.Var):      # an operand, or a bare BOOL attribute as its own condition
+        d = ctx.app.streams[ctx.stream_ids[s]]
+        ai = d.attr_index(e.attr)
+        t = d.attrs[ai][1]
+        col = column_layout(ctx).index((s, ai, t))
+        return [OP_VAR, 0, 0, col, TYPE_CODE[t]], t
+    if isinstance(e, C.Compare):
+        lw, lt = _range_prog(ctx, s, e.left)
+        rw, rt = _range_prog(ctx, s, e.right)
+        return lw + rw + [OP_CMP, CMP_CODE[e.op], _cmp_domain(lt, rt, e.op)], "BOOL"
+    if isinstance(e, (C.And, C.Or)):
+        return (_range_prog(ctx, s, e.left)[0] + _range_prog(ctx, s, e.right)[0] +
+                [OP_AND if isinstance(e, C.And) else OP_OR]), "BOOL"
+    if isinstance(e, (C.Not, C.IsNull)):
+        return _range_prog(ctx, s, e.expr)[0] + [OP_NOT if isinstance(e, C.Not) else OP_ISNULL], "BOOL"
+    raise LoweringError(f"unsupported expression in a range condition: {e}")
+
+
+def lower_ranges(ctx: QueryContext) -> Optional[RangeTable]:
+    """The query's range partitions for the device router, or None when no stream has ranges."""
+    labels: List[str] = []
+    ranges = []
+    for s, rl in enumerate(ctx.key_ranges):
+        for cond, label in (rl or []):
+            if label not in labels:
+                labels.append(label)
+            ranges.append((s, labels.index(label), _range_prog(ctx, s, cond)[0]))
+    if not ranges:
+        return None
+    if len(ranges) > MAX_RANGES:
+        raise LoweringError(f"more than {MAX_RANGES} ranges in a partition")
+    if sum(len(p) for _, _, p in ranges) > MAX_CODE:
+        raise LoweringError("range condition programs too long")
+    return RangeTable(1 if ctx.app.playback else 0, column_layout(ctx), labels, ranges)

@@ -221,7 +221,8 @@ def _range_mask(e, d: C.StreamDefinition, cols: dict, nulls: dict, strings: dict
     """RangePartitionExecutor's condition (C/partition/executor/RangePartitionExecutor.java:38-43) over n rows, with
     the compare executors' rules: a null operand makes a compare false and `!=` true (CompareConditionExpression
     Executor.java:39-43, NotEqualCompareConditionExpressionExecutor.java:37); numbers compare in the wider of the
-    two types (INT / LONG as LONG, with a FLOAT as FLOAT, with a DOUBLE as DOUBLE: Java binary promotion)."""
+    two types (INT / LONG as LONG, with a FLOAT as FLOAT, with a DOUBLE as DOUBLE: Java binary promotion), except
+    == / != of a FLOAT and a LONG, which compare as DOUBLE."""
     if isinstance(e, C.And):
         return _range_mask(e.left, d, cols, nulls, strings, n) & _range_mask(e.right, d, cols, nulls, strings, n)
     if isinstance(e, C.Or):
@@ -237,12 +238,10 @@ def _range_mask(e, d: C.StreamDefinition, cols: dict, nulls: dict, strings: dict
     rv, rt, rn = _range_value(e.right, d, cols, nulls, strings, n)
     if (lt in ("STRING", "BOOL") or rt in ("STRING", "BOOL")) and (lt != rt or e.op not in ("==", "!=")):
         raise SiddhiAppCreationException(f"range partition: cannot compare {lt} {e.op} {rt}")
-    if "DOUBLE" in (lt, rt):
-        lv, rv = lv.astype(np.float64), rv.astype(np.float64)
-    elif "FLOAT" in (lt, rt):
-        lv, rv = lv.astype(np.float32), rv.astype(np.float32)
-    else:
-        lv, rv = lv.astype(np.int64), rv.astype(np.int64)
+    # the compare domain is the filters' (lowering._cmp_domain): == / != between a FLOAT and a LONG compare as
+    # doubles (EqualCompareConditionExpressionExecutorLongFloat.java:36-38), not in the wider type
+    dt = {L.D_F64: np.float64, L.D_F32: np.float32}.get(L._cmp_domain(lt, rt, e.op), np.int64)
+    lv, rv = lv.astype(dt), rv.astype(dt)
     r = {"==": np.equal, "!=": np.not_equal, ">": np.greater, ">=": np.greater_equal, "<": np.less,
          "<=": np.less_equal}[e.op](lv, rv)
     anynull = ln | rn
@@ -413,6 +412,9 @@ class SiddhiAppRuntime:
         self.next_index = 0
         self.started = False
         self.persistence_store: Optional[PersistenceStore] = None
+        # send_columns routes range partitions on the engine's device where the engine has a range router
+        # (GpuEngine.range_router); False keeps the host router (_route_ranges) for every batch
+        self.device_ranges = True
 
     # -- API
     def getInputHandler(self, stream_id: str) -> InputHandler:
@@ -559,12 +561,29 @@ class SiddhiAppRuntime:
                 key = np.zeros(n, np.int32) if not q.ctx.partitioned else np.full(n, -1, np.int32)
             b = Batch(n, base, ts, stream_col, key, allcols, nulls)
             if q.ctx.partitioned and q.ctx.key_ranges[stream] is not None:
+                if self.device_ranges and getattr(q.engine, "range_router", None) is not None:
+                    self._push_ranges(qi, q, b)
+                    self._deliver(q, q.engine.fetch())
+                    continue
                 b = self._route_ranges(qi, q, b, stream_col)
             if stream in q.global_streams:
                 b = _broadcast(b, np.ones(n, bool), len(self.key_dicts[qi]))
             if b.n:
                 q.engine.push(b)
             self._deliver(q, q.engine.fetch())
+
+    def _push_ranges(self, qi: int, q: "_QueryRuntime", b: "Batch"):
+        """Route the batch's rows of range-partitioned streams on the engine's device (GpuEngine.push_ranges) and push
+        them.  The key dictionary stays the only owner of ids: the labels' keys go in, the labels first held in this
+        batch come back with the next free ids in first-seen order (what _range_route's key_of_label hands out)."""
+        kd = self.key_dicts[qi]
+        labels = q.engine.range_labels
+        label_key = np.array([kd.get(lab, -1) for lab in labels], np.int32)
+        first = len(kd)
+        after = q.engine.push_ranges(b, label_key, first)
+        new = {int(label_key[c]): lab for c, lab in enumerate(labels) if label_key[c] >= first}
+        for k in range(first, after):    # (insertion order is id order: snapshot() stores the keys as a list)
+            kd[new[k]] = k
 
     def _route_ranges(self, qi: int, q: "_QueryRuntime", b: "Batch", stream: np.ndarray) -> "Batch":
         """the batch's rows of range-partitioned streams, one copy per holding range (_range_route)"""
