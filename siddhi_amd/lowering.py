@@ -83,6 +83,12 @@ def make_context(app: C.SiddhiApp, query: C.Query, partition: Optional[C.Partiti
     return ctx
 
 
+def _range_attr_type(d: C.StreamDefinition, x: C.Var) -> str:
+    if x.stream_ref not in (None, d.id) or x.index is not None or d.attr_index(x.attr) < 0:
+        raise LoweringError(f"range partition condition: {x.attr} is not an attribute of {d.id}")
+    return d.attr_type(x.attr)
+
+
 def _check_range_cond(d: C.StreamDefinition, e):
     """A range partition's condition reads the partitioned stream's own attributes (RangePartitionExecutor runs it
     on the arriving event, C/partition/executor/RangePartitionExecutor.java:38-43): compares, and / or / not and
@@ -90,15 +96,19 @@ def _check_range_cond(d: C.StreamDefinition, e):
     if isinstance(e, (C.And, C.Or)):
         _check_range_cond(d, e.left)
         _check_range_cond(d, e.right)
-    elif isinstance(e, (C.Not, C.IsNull)):
+    elif isinstance(e, C.Not):
         _check_range_cond(d, e.expr)
+    elif isinstance(e, C.IsNull):
+        # the operand is a value, not a condition: an attribute of any type (IsNullConditionExpressionExecutor runs
+        # whatever executor it is given, C/executor/condition/IsNullConditionExpressionExecutor.java:35-41)
+        if not isinstance(e.expr, C.Var):
+            raise LoweringError("range partition condition: `is null` of an attribute only")
+        _range_attr_type(d, e.expr)
     elif isinstance(e, C.Compare):
         ts = []
         for x in (e.left, e.right):
             if isinstance(x, C.Var):
-                if x.stream_ref not in (None, d.id) or x.index is not None or d.attr_index(x.attr) < 0:
-                    raise LoweringError(f"range partition condition: {x.attr} is not an attribute of {d.id}")
-                ts.append(d.attr_type(x.attr))
+                ts.append(_range_attr_type(d, x))
             elif isinstance(x, C.Const):
                 ts.append(x.type)
             else:

@@ -188,7 +188,9 @@ def _broadcast(b: "Batch", bcast: np.ndarray, keys_before: int) -> "Batch":
     exists when they arrive (PartitionStreamReceiver.receive with no partition executor -> send(event) to every
     cached per-key junction, C/partition/PartitionStreamReceiver.java:83-92,277-281): such a row (bcast) becomes one
     row per key seen before it, all with the row's event index.  The reference visits the instances in its
-    ConcurrentHashMap order; here they come in first-seen key order (the order every other per-trigger tie uses)."""
+    ConcurrentHashMap order; here they come in first-seen key order (the order every other per-trigger tie uses).
+    "Seen before it" is read off the ids: the caller hands them out in order of first appearance over the rows, value
+    keys and range labels alike (flush), so the instances of a row's moment are 0 .. the highest id so far."""
     n = b.n
     seen = np.maximum.accumulate(np.where(bcast, -1, b.key.astype(np.int64)))   # highest id seen so far
     before = np.maximum(np.concatenate([[keys_before - 1], seen[:-1]]), keys_before - 1) + 1
@@ -585,27 +587,48 @@ class SiddhiAppRuntime:
         for k in range(first, after):    # (insertion order is id order: snapshot() stores the keys as a list)
             kd[new[k]] = k
 
-    def _route_ranges(self, qi: int, q: "_QueryRuntime", b: "Batch", stream: np.ndarray) -> "Batch":
-        """the batch's rows of range-partitioned streams, one copy per holding range (_range_route)"""
+    def _route_ranges(self, qi: int, q: "_QueryRuntime", b: "Batch", stream: np.ndarray, masks=None) -> "Batch":
+        """the batch's rows of range-partitioned streams, one copy per holding range (_range_route); masks: what
+        _range_masks gave for this batch, where the caller has it already"""
         kd = self.key_dicts[qi]
 
+        # Called without masks (send_columns, one stream per batch), a label takes its id here, the moment
+        # _range_route first meets a row that holds it.  flush() passes its masks and has by then given every held
+        # label its id in its row-order pass over value keys and labels, so here key_of_label only looks ids up.
         def key_of_label(label):
             i = kd.get(label)
             if i is None:
                 i = len(kd)
                 kd[label] = i
             return i
+        masks = self._range_masks(q, b.cols, b.nulls, stream, b.n) if masks is None else masks
+        return _range_route(b, stream, masks, key_of_label, clock=bool(self.app.playback)) if masks else b
+
+    def _range_masks(self, q: "_QueryRuntime", allcols: list, allnulls: list, stream: np.ndarray, n: int) -> dict:
+        """stream index -> (labels, bool[n_ranges, n]): every range condition of the query over the batch's rows"""
         masks = {}
         for s, rl in enumerate(q.ctx.key_ranges):
             if rl is None or not (stream == s).any():
                 continue
             d = self.app.streams[self.stream_ids[s]]
             cb = self._col_base(s)
-            cols = {name: b.cols[cb + a] for a, (name, _) in enumerate(d.attrs)}
-            nulls = {name: b.nulls[cb + a] for a, (name, _) in enumerate(d.attrs) if b.nulls[cb + a] is not None}
-            m = np.stack([_range_mask(c, d, cols, nulls, self.strings, b.n) for c, _ in rl])
+            cols = {name: allcols[cb + a] for a, (name, _) in enumerate(d.attrs)}
+            nulls = {name: allnulls[cb + a] for a, (name, _) in enumerate(d.attrs) if allnulls[cb + a] is not None}
+            m = np.stack([_range_mask(c, d, cols, nulls, self.strings, n) for c, _ in rl])
             masks[s] = ([lab for _, lab in rl], m)
-        return _range_route(b, stream, masks, key_of_label, clock=bool(self.app.playback)) if masks else b
+        return masks
+
+    @staticmethod
+    def _first_holders(kd: dict, masks: dict, stream: np.ndarray) -> dict:
+        """row -> the labels without an id whose first holding row it is (a row's labels in written order)"""
+        due = {}
+        for s, (labels, m) in masks.items():
+            rows = stream == s
+            for ri, lab in enumerate(labels):
+                hit = m[ri] & rows
+                if lab not in kd and hit.any():
+                    due.setdefault(int(np.argmax(hit)), []).append(lab)
+        return due
 
     def _col_base(self, stream: int) -> int:
         return sum(len(self.app.streams[sid].attrs) for sid in self.stream_ids[:stream])
@@ -671,12 +694,24 @@ class SiddhiAppRuntime:
         for qi, q in enumerate(self.queries):
             key = np.full(n, -1, dtype=np.int32)
             bcast = None
+            masks = None
             if q.ctx.partitioned:
                 kd = self.key_dicts[qi]
                 keys_before = len(kd)
                 if q.global_streams:
                     bcast = np.fromiter((r[0] in q.global_streams for r in rows), dtype=bool, count=n)
+                # An instance exists from the row that first needs it (PartitionStreamReceiver.send ->
+                # cloneIfNotExist, C/partition/PartitionStreamReceiver.java:270-275), whether a value key or a range
+                # label asks for it: both take their ids in this one pass over the rows, so ids grow in order of
+                # first appearance -- what _broadcast reads the instances of a row's moment from.
+                due = {}
+                if any(r is not None for r in q.ctx.key_ranges):
+                    masks = self._range_masks(q, cols, nulls, stream, n)
+                    due = self._first_holders(kd, masks, stream)
                 for i, r in enumerate(rows):
+                    for lab in due.get(i, ()):
+                        if lab not in kd:
+                            kd[lab] = len(kd)
                     s = r[0]
                     if s < 0 or q.ctx.key_attr[s] < 0:
                         continue
@@ -693,8 +728,8 @@ class SiddhiAppRuntime:
             else:
                 key[:] = 0
             b = Batch(n, base, ts, stream, key, cols, nulls)
-            if q.ctx.partitioned and any(r is not None for r in q.ctx.key_ranges):
-                b = self._route_ranges(qi, q, b, stream)
+            if masks is not None:
+                b = self._route_ranges(qi, q, b, stream, masks)
                 if q.global_streams:
                     bcast = np.isin(b.stream, list(q.global_streams))
             if bcast is not None and bcast.any():

@@ -6,7 +6,10 @@ kernel evaluates the programs per row and the expand kernel writes one copy per 
 programs against the host masks with a numpy interpreter of the postfix code written here, the FLOAT/LONG equality rule
 against a hand-derived value, and the ABI's struct layout against C.  The GPU tests compare the routed device batch
 with _range_route over _range_mask field by field, and with rows written out by hand, then run whole apps through
-send_columns on both routes."""
+send_columns on both routes.  Both routers share lowering._cmp_domain, so a second group of GPU tests takes its
+expected values from range_ref.py, a row-at-a-time restatement that shares no code with either: every type and compare
+domain on edge values, every instantiation of the hold kernel, first holders in other waves and tiles than the first,
+and the optional arrays of the batch left out."""
 import ctypes as ct
 import os
 import struct
@@ -18,6 +21,8 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
 
+import range_cases as RC  # noqa: E402
+import range_ref  # noqa: E402
 from oracle import OracleEngine  # noqa: E402  (checker engine; CPU)
 from siddhi_amd import QueryCallback, SiddhiManager  # noqa: E402
 from siddhi_amd import compiler as C  # noqa: E402
@@ -238,21 +243,26 @@ class Harness:
             assert self.hip.hipMemcpy(ct.c_void_p(a.ctypes.data), ct.c_void_p(ptr), ct.c_size_t(a.nbytes), 2) == 0
         return a
 
-    def device(self, b, keys, device_input=False):
+    def device(self, b, keys, device_input=False, no_stream=False, no_key=False, no_index=False, no_nulls=False):
         """route b on the device with the key dictionary `keys` (label / key string -> id; updated like the host's):
-        the routed batch copied back, as a Batch plus its key_bound"""
+        the routed batch copied back, as a Batch plus its key_bound.  no_stream / no_key / no_index pass that array of
+        the sg_batch as NULL (every row stream 0 / key -1 / index base_index + row), no_nulls the array of null
+        arrays itself (b must then have no null array)."""
         N = self.N
         labels = self.table.labels
         label_key = np.array([keys.get(lab, -1) for lab in labels], np.int32)
         first = len(keys)
-        kb = int(b.key.max()) + 1 if b.n and b.key.max() >= 0 else 0
+        kb = int(b.key.max()) + 1 if b.n and b.key.max() >= 0 and not no_key else 0
         keep = []
+        assert not no_nulls or all(x is None for x in b.nulls)
+        stream, key = (None if no_stream else b.stream), (None if no_key else b.key)
+        index = None if no_index else b.index
         if device_input:
             import torch
             dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
             ptr = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-            idx = None if b.index is None else dev(b.index.view(np.int64))
-            t = [dev(b.ts), dev(b.stream), dev(b.key), idx] + [dev(c) for c in b.cols] + [dev(x) for x in b.nulls]
+            idx = None if index is None else dev(index.view(np.int64))
+            t = [dev(b.ts), dev(stream), dev(key), idx] + [dev(c) for c in b.cols] + [dev(x) for x in b.nulls]
             keep.append(t)
             torch.cuda.synchronize()
             nc = len(b.cols)
@@ -260,8 +270,10 @@ class Harness:
                               [ptr(x) for x in t[4 + nc:]], 1, kb, keep, index=ptr(t[3]))
         else:
             ptr = lambda a: 0 if a is None else a.ctypes.data   # noqa: E731
-            sb = N.make_batch(b.n, b.base_index, ptr(b.ts), ptr(b.stream), ptr(b.key), [ptr(c) for c in b.cols],
-                              [ptr(x) for x in b.nulls], 0, kb, keep, index=ptr(b.index))
+            sb = N.make_batch(b.n, b.base_index, ptr(b.ts), ptr(stream), ptr(key), [ptr(c) for c in b.cols],
+                              [ptr(x) for x in b.nulls], 0, kb, keep, index=ptr(index))
+        if no_nulls:
+            sb.nulls = None
         out, after = self.router.route(sb, label_key, first)
         assert out.on_device == 1 and out.base_index == b.base_index
         new = {int(label_key[c]): lab for c, lab in enumerate(labels) if label_key[c] >= first}
@@ -302,6 +314,23 @@ class Harness:
         lab = [dk[x] for x in self.table.labels if x in dk]
         assert key_bound == max(kb_in, 1 + max(lab) if lab else 0)
         return got
+
+    def check_reference(self, rows, b, keys=None, device_input=False, want=None, **null_arrays):
+        """device route of b == range_ref.route of `rows` (the rows b was built from; `want` where the caller has
+        routed them already), field by field, and the same dictionary in the same creation order; returns (the
+        device's batch, the reference's routing)"""
+        dk = {} if keys is None else dict(keys)
+        given = None if b.index is None or null_arrays.get("no_index") else b.index
+        if want is None:
+            want = range_ref.route(self.rt.app, rows, keys=list(dk), base_index=b.base_index, indices=given,
+                                   broadcast=False)
+        got, key_bound = self.device(b, dk, device_input, **null_arrays)
+        assert list(dk) == want.keys
+        RC.assert_routed(got, want, b, self.rt.app, self.rt.strings)
+        kb_in = int(b.key.max()) + 1 if b.n and b.key.max() >= 0 and not null_arrays.get("no_key") else 0
+        lab = [dk[x] for x in self.table.labels if x in dk]
+        assert key_bound == max(kb_in, 1 + max(lab) if lab else 0)
+        return got, want
 
 
 _harness = {}
@@ -503,6 +532,182 @@ def test_router_refuses_a_bad_descriptor():
     assert e.value.code == N.SG_EUNSUPPORTED
 
 
+# ------------------------------------------------------------------------------------------- GPU: against range_ref
+# Expected values below come from range_ref.route, the row-at-a-time restatement that shares no code with either router.
+@pytest.mark.gpu
+@pytest.mark.parametrize("device_input", [False, True])
+@pytest.mark.parametrize("k", range(len(RC.TYPED_APPS)))
+def test_router_types_and_domains_equal_reference(k, device_input):
+    """the all-type apps of test_range_reference.py (column pairs x operators, edge constants, STRING / BOOL, `is null`,
+    nested forms; edge-value pools with nulls) on the device"""
+    case = RC.typed_case(k)
+    h = harness(case.text)
+    b = RC.batch_of(h.rt.app, case.rows, h.rt.strings, base=500)
+    h.check_reference(case.rows, b, None, device_input, want=case.want)
+
+
+def prog_depth(prog):
+    """operand stack depth of a postfix range program (what sg_range_open sizes the hold kernel's stack from)"""
+    sp = mx = pc = 0
+    while pc < len(prog):
+        op = prog[pc]
+        push, words = {L.OP_VAR: (1, 5), L.OP_CONST: (1, 3), L.OP_CMP: (-1, 3), L.OP_AND: (-1, 1), L.OP_OR: (-1, 1),
+                       L.OP_NOT: (0, 1), L.OP_ISNULL: (0, 1)}[op]
+        sp, pc = sp + push, pc + words
+        mx = max(mx, sp)
+    return mx
+
+
+# atoms of every operand type (depth <= 2 each); the innermost one compares a LONG with a FLOAT column, both with nulls,
+# so at the deepest point the stack holds truth values, an i64 and an f64 operand and null flags at once
+ATOMS = ["i>0", "f<3.0", "l is null", "d>=0.5", "b", "s!='abc'", "i2!=2", "not (f2 is null)", "l>f", "d2<2.0", "i==f",
+         "l2!=9007199254740993l", "f2>=d", "i<=l"]
+INNERMOST = "l2<=f2"
+
+
+def nested(m):
+    """(c1 and (c2 or (c3 and ... cm))), right-nested: every level keeps one more truth value on the stack, so m
+    atoms need depth m + 1"""
+    atoms = ATOMS[:m - 1] + [INNERMOST]
+    e = atoms[-1]
+    for j in range(m - 2, -1, -1):
+        e = f"({atoms[j]} {'and' if j % 2 == 0 else 'or'} {e})"
+    return e
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("device_input", [False, True])
+@pytest.mark.parametrize("depth", [2, 4, 8, 16])
+def test_router_every_hold_kernel_depth(depth, device_input):
+    """launch_hold picks k_rr_hold<2 | 4 | 8 | 16> from the deepest program: one app per instantiation"""
+    text = RC.TYPED.format(f"{nested(depth - 1)} as 'deep' or i>0 as 'pos' or l is null as 'nul'")
+    h = harness(text)
+    assert max(prog_depth(p) for _, _, p in h.table.ranges) == depth
+    assert sum(len(p) for _, _, p in h.table.ranges) <= L.MAX_CODE
+    rows = RC.typed_rows(1000, 40 + depth)
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=7)
+    _, want = h.check_reference(rows, b, None, device_input)
+    deep = sum(1 for r in want.rows if want.keys[r[2]] == "deep")
+    assert 0 < deep < len(rows)
+
+
+FIRST = ("define stream S (a int, b int, c int, r int); partition with ({} of S) begin @info(name='q') "
+         "from every e1=S -> e2=S[a>e1.a] select e1.a as a insert into M; end;")
+FIRST_LABELS = {2: FIRST.format("a>0 as 'A' or b>0 as 'B'"), 3: FIRST.format("a>0 as 'A' or b>0 as 'B' or c>0 as 'C'")}
+
+
+def first_rows(n, firsts):
+    """rows of S whose column j is 0 before row firsts[j] and 1 in that row: label j is first held in row firsts[j].
+    After it the label that comes q-th in first-held order holds every row with row % 8 == 6 - 2 q, so in every later
+    wave and tile the labels' first holders come in the REVERSE order: a router that read a label's first holder from
+    a later wave or tile than the first would hand out other ids.  Column r is the row number."""
+    order = sorted(range(len(firsts)), key=lambda j: (firsts[j], j))
+    return [(0, 2 * r, [int(r == f or (r > f and r % 8 == 6 - 2 * order.index(j))) for j, f in enumerate(firsts)] +
+             [0] * (3 - len(firsts)) + [r]) for r in range(n)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("firsts", [(63, 64), (64, 63), (255, 256), (256, 255), (191, 192), (300, 300), (599, 0),
+                                    (512, 511), (256, 255, 64), (300, 300, 300), (599, 0, 320), (130, 447, 129)])
+def test_router_first_holders_away_from_row_zero(firsts):
+    """three tiles of 256 rows; the first holders sit in other waves than wave 0 and other tiles than tile 0, on both
+    sides of a wave and a tile border: the per-wave table, the lowest-wave loop and the minimum across tiles decide the
+    ids.  A row that holds two new labels gives them ids in written order."""
+    h = harness(FIRST_LABELS[len(firsts)])
+    rows = first_rows(600, firsts)
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=100)
+    got, want = h.check_reference(rows, b)
+    order = sorted(range(len(firsts)), key=lambda j: (firsts[j], j))       # by hand: first row, then written order
+    assert want.keys == ["ABC"[j] for j in order]
+    for j, f in enumerate(firsts):
+        copies = got.key == order.index(j)
+        assert int(got.index[copies].min()) == 100 + f and copies.sum() >= 1 + (599 - f) // 8
+
+
+@pytest.mark.gpu
+def test_router_first_holder_with_one_label_known():
+    """'A' is in the dictionary (label_key >= 0: the hold kernel skips it), 'B' is new and first held in tile 1"""
+    h = harness(FIRST_LABELS[2])
+    rows = first_rows(600, (130, 447))
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=0)
+    got, want = h.check_reference(rows, b, {"k0": 0, "A": 1, "k2": 2})
+    assert want.keys == ["k0", "A", "k2", "B"] and set(got.key.tolist()) == {1, 3}
+
+
+@pytest.mark.gpu
+def test_router_32_labels_first_held_in_reverse_written_order():
+    """label k is first held in row 560 - 17 k: the ids come out in row order, the reverse of the written order"""
+    h = harness(FIRST.format(" or ".join(f"r>={560 - 17 * k} as 'l{k}'" for k in range(32))))
+    rows = first_rows(600, ())
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=0)
+    got, want = h.check_reference(rows, b)
+    assert want.keys == [f"l{k}" for k in range(31, -1, -1)]
+    assert got.n == sum(600 - (560 - 17 * k) for k in range(32))
+
+
+def shared_rows(n=600):
+    """S (even rows) holds 'lo' from row 0 and 'hi' from row 400 on; T (odd rows) holds 'lo', 'hi' from row 71 on and
+    'small' from row 301 on: 'hi' is first held through T's range, written after S's, in an earlier row"""
+    rng = np.random.default_rng(2)
+    rows = []
+    for r in range(n):
+        u = rng.random()
+        if r % 2 == 0:
+            rows.append((0, r, [50.0 if r >= 400 and (r == 400 or u < 0.5) else 20.0]))
+        elif r >= 301 and (r == 301 or u < 0.3):
+            rows.append((1, r, [5.0]))
+        else:
+            rows.append((1, r, [40.0 if r >= 71 and (r == 71 or u < 0.65) else 15.0]))
+    return rows
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("device_input", [False, True])
+def test_router_label_shared_by_two_streams_first_held_through_the_later_one(device_input):
+    h = harness(SHARED)
+    rows = shared_rows()
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=0)
+    got, want = h.check_reference(rows, b, None, device_input)
+    assert want.keys == ["lo", "hi", "small"]            # rows 0, 71 and 301
+    hi = got.key == 1
+    assert int(got.index[hi].min()) == 71 and set(got.stream[hi].tolist()) == {0, 1}
+
+
+UNRANGED = ("define stream S (a int, b int); define stream U (u int); partition with (a>0 as 'A' or b>0 as 'B' of S) "
+            "begin @info(name='q') from every e1=S -> e2=U[u>e1.a] select e1.a as a insert into M; end;")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("device_input", [False, True])
+@pytest.mark.parametrize("absent", ["stream", "key", "index", "nulls", "none"])
+def test_router_optional_arrays(absent, device_input):
+    """sg_batch.stream / key / index and the array of null arrays may each be NULL"""
+    rng = np.random.default_rng(5)
+    n = 700
+    if absent == "key":          # rows of U pass through with key -1
+        h = harness(UNRANGED)
+        rows = [(0, r, [int(rng.integers(0, 2)), int(rng.integers(-1, 2))]) if rng.random() < 0.6 else (1, r, [r])
+                for r in range(n)]
+    elif absent == "nulls":
+        h = harness(RC.TYPED.format(f"{nested(3)} as 'deep' or i>0 as 'pos' or f2>=d as 'fd'"))
+        rows = RC.typed_rows(n, 9, null_rate=0.0)
+    else:
+        h = harness(FIRST_LABELS[2])
+        rows = first_rows(n, (130, 70))
+    index = None
+    if absent in ("index", "none"):      # given here, and left out below for "index"
+        index = np.uint64(9000) + np.cumsum(rng.integers(1, 4, n)).astype(np.uint64)
+    b = RC.batch_of(h.rt.app, rows, h.rt.strings, base=50, index=index)
+    got, want = h.check_reference(rows, b, None, device_input, **({} if absent == "none" else {f"no_{absent}": True}))
+    assert got.n > n // 8
+    if absent == "key":
+        assert set(got.key[got.stream == 1].tolist()) == {-1} and (got.stream == 1).sum() == sum(s for s, _, _ in rows)
+    if absent == "index":
+        assert got.index.max() < 50 + n
+    if absent == "none":
+        assert got.index.min() > 9000
+
+
 # ------------------------------------------------------------------------------------------- GPU: end to end
 def run_columns(engine, text, sends, device_ranges=True, snapshot_after=None):
     """send_columns every (stream, cols) of `sends`; returns (delivered rows, rows the engine was pushed, the range
@@ -602,3 +807,50 @@ def test_e2e_second_call_introduces_a_label_and_snapshot_between_calls():
     text = app(within="within 1 sec")
     e2e(text, sends, 200)
     e2e(text, sends, 200, snapshot_after=1)
+
+
+@pytest.mark.gpu
+def test_e2e_is_null_of_a_float_attribute_column_path():
+    """`is null` of a FLOAT attribute in a range condition (refused before the fix in lowering._check_range_cond), alone
+    and under not / and, through send_columns on the device route and the host route.  send_columns carries no nulls,
+    so no row holds 'missing' and `not (price is null)` holds on every row: this shows that the app is accepted and
+    that ISNULL is false on the device for a column without a null array.  Rows that hold 'missing' are routed on the
+    device in the typed apps above and run end to end in the row-path test below."""
+    rows = [r for r in _random_rows(2000, 5) if r[1][1] is not None]
+    ranges = "price is null as 'missing' or not (price is null) and price>=30 as 'hi' or price<30 as 'lo'"
+    e2e(app(ranges, within="within 1 sec"), [("S", price_columns(rows))], 100)
+
+
+IS_NULL_ROWS_APP = ("define stream S (symbol string, price float, volume int); "
+                    "partition with (price is null as 'missing' or not (price is null) and price>=30 as 'hi' or "
+                    "price<30 as 'lo' of S) begin @info(name='q') from every e1=S -> e2=S[volume>e1.volume] "
+                    "select e1.volume as v1, e2.volume as v2, e2.price as p2 insert into M; end;")
+
+
+@pytest.mark.gpu
+def test_e2e_is_null_of_a_float_attribute_row_path_with_null_prices():
+    """the same ranges on the row path, which carries nulls: about 30 % of the rows have no price and hold 'missing'.
+    The MI355X engine is pushed the reference router's copies, 'missing' gets its id in the reference's place, and it
+    delivers what the oracle engine delivers, matches inside 'missing' (p2 null) among them."""
+    from siddhi_amd._native import GpuEngine
+    rows = RC.price_rows(2000, 5)
+    assert 400 < sum(v[1] is None for _, _, v in rows) < 800
+    assert "missing" in range_ref.route(C.parse(IS_NULL_ROWS_APP), rows).keys
+    want = RC.check_flush_granularity(OracleEngine, IS_NULL_ROWS_APP, rows, 100, plans={"one flush": set()})
+    assert sum(d[2] is None for _, d in want) >= 20 and sum(d[2] is not None for _, d in want) >= 20
+    RC.check_flush_granularity(GpuEngine, IS_NULL_ROWS_APP, rows, delivered=want,
+                               plans=RC.flush_plans(len(rows), every_row=False, pieces=40))
+
+
+@pytest.mark.gpu
+def test_e2e_mixed_flush_row_path():
+    """value keys, range labels and an unpartitioned stream in one partition on the row path: however the rows are
+    flushed, the MI355X engine is pushed the reference router's copies and delivers what the oracle engine delivers
+    when every row is flushed on its own"""
+    from siddhi_amd._native import GpuEngine
+    three = [(1, 0, [1]), (2, 1, [7]), (0, 2, [5])]
+    assert RC.check_flush_granularity(GpuEngine, RC.MIXED3, three) == []
+    rows = RC.mixed_rows(2000, 8, rate=0.01)
+    want = RC.check_flush_granularity(OracleEngine, RC.MIXED, rows, 200, plans={"every row": set(range(len(rows)))})
+    RC.check_flush_granularity(GpuEngine, RC.MIXED, rows, plans=RC.flush_plans(len(rows), every_row=False, pieces=40),
+                               delivered=want)
