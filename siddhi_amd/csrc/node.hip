@@ -492,6 +492,17 @@ struct XGpu {
   hipEvent_t ev_in[2] = {}, ev_scat[2] = {}, ev_sent[2] = {}, ev_rfree[2] = {}, ev_osent[2] = {}, ev_mfree[2] = {},
              ev_d2h[2] = {};
   bool init = false;
+  // room for nk entries in l2g: a larger table takes over the l2g_n entries of the old one (st: the stream whose
+  // queued work reads the table; it is drained first)
+  void l2g_reserve(int64_t nk, hipStream_t st) {
+    if ((size_t)nk * 4 <= l2g.bytes) return;
+    HIPCHK(hipStreamSynchronize(st));
+    XBuf nb;
+    nb.ensure((size_t)(nk + nk / 2 + 1024) * 4);
+    if (l2g_n) HIPCHK(hipMemcpy(nb.p, l2g.p, 4 * (size_t)l2g_n, hipMemcpyDeviceToDevice));
+    l2g.release();
+    l2g = nb;
+  }
   void release() {
     for (int p = 0; p < 2; ++p) {
       in[p].buf.release();
@@ -545,8 +556,8 @@ struct sg_node {
   int64_t local_rows[MAX_GPUS] = {};   // rows each shard has seen (its local event index space)
   int64_t next_index = 0;
   bool broken = false;
-  bool no_fill = false;
-  bool no_ts32 = false;              // testing: timestamps always travel as 8 bytes              // testing: ship every column back instead of filling trigger-row columns on the host
+  bool no_fill = false;              // testing: ship every column back instead of filling trigger-row columns on the host
+  bool no_ts32 = false;              // testing: timestamps always travel as 8 bytes
   // per-GPU device-side ingress slots and copy stream
   hipStream_t cp[MAX_GPUS] = {};
   hipEvent_t ev_copied[MAX_GPUS][2] = {}, ev_used[MAX_GPUS][2] = {};
@@ -637,6 +648,17 @@ inline void fill_row(const sg_node_batch& b, const sg_nfa_desc& d, const Want& w
   (void)d;
 }
 
+// Steps of the GPU-side shard exchange that another GPU's thread waits for (Run::x_pass / x_wait), in chunk order.
+enum XStep {
+  X_COUNTED,   // send starts per shard known (xst)
+  X_SENT,      // row pieces queued to every shard's receive slot (ev_sent recorded)
+  X_USED,      // the shard's rows computed (ev_rfree recorded); its new keys' first rows published (xnf, xkbase)
+  X_PIECED,    // match bounds per slice known (xpc)
+  X_MREADY,    // the owner's merge input has room for its pieces
+  X_OSENT,     // match pieces queued to every owner (ev_osent recorded)
+  N_XSTEPS
+};
+
 // Pipeline state of one sg_node_push call.
 struct Run {
   sg_node& nd;
@@ -666,12 +688,13 @@ struct Run {
   std::vector<int64_t> ts_base_of;
   std::vector<uint8_t> ts32_of;
   double t_route = 0, t_merge = 0, t_gpu[MAX_GPUS] = {};
-  // GPU-side shard exchange (x_loop): per (chunk, GPU) send starts per shard and match bounds per slice (G + 1 each),
-  // new keys' first global rows; per GPU the chunks past each step
+  // GPU-side shard exchange (x_loop): the columns that travel; per (chunk, GPU) send starts per shard and match bounds
+  // per slice (G + 1 each, x_row), new keys' first global rows and the shard's key count before them; per step and
+  // GPU the chunks past it (x_pass / x_wait); the chunks whose node-wide key ids are assigned
+  XSpec xsp;
   std::vector<int64_t> xst, xpc, xkbase;
   std::vector<std::vector<uint64_t>> xnf;
-  int64_t xcounted[MAX_GPUS] = {}, xsent[MAX_GPUS] = {}, xused[MAX_GPUS] = {}, xnfp[MAX_GPUS] = {},
-          xpieced[MAX_GPUS] = {}, xmready[MAX_GPUS] = {}, xosent[MAX_GPUS] = {};
+  int64_t xstep[N_XSTEPS][MAX_GPUS] = {};
   int64_t xids = 0;
   int64_t h2d_bytes = 0, d2h_bytes = 0;
 
@@ -700,6 +723,36 @@ struct Run {
     }
     cv.notify_all();
   }
+  // The exchange's one barrier.  x_pass: GPU g's thread runs f under the lock, is then past step S of chunk j, and
+  // wakes the waiters; x_wait: until every GPU is past step S of chunk j, or failure (false).
+  template <class F>
+  void x_pass(XStep S, int g, int64_t j, F f) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      f();
+      xstep[S][g] = j + 1;
+    }
+    cv.notify_all();
+  }
+  void x_pass(XStep S, int g, int64_t j) { x_pass(S, g, j, [] {}); }
+  bool x_past(XStep S, int64_t j) const {   // (a wait's predicate: under the lock)
+    for (int q = 0; q < nd.G; ++q)
+      if (xstep[S][q] <= j) return false;
+    return true;
+  }
+  bool x_wait(XStep S, int64_t j) {
+    return wait([&] { return x_past(S, j); });
+  }
+  // The G + 1 entries of (chunk j, GPU g) in xst or xpc.  Who may touch a (chunk, GPU) row of xst / xpc / xnf / xkbase:
+  // only GPU g's thread writes it, inside the x_pass that puts g past that step (X_COUNTED for xst, X_USED for xnf and
+  // xkbase, X_PIECED for xpc); the other threads read it, outside the lock, only after an x_wait (or a wait on
+  // x_past) that saw g past that step -- the mutex orders the write before the read.
+  int64_t* x_row(std::vector<int64_t>& t, int64_t j, int g) { return &t[(size_t)(j * nd.G + g) * (nd.G + 1)]; }
+  // entry q of that row as a count: xst -- the rows GPU g's slice sends shard q; xpc -- shard g's matches for owner q
+  int64_t x_cnt(std::vector<int64_t>& t, int64_t j, int g, int q) {
+    const int64_t* e = x_row(t, j, g);
+    return e[q + 1] - e[q];
+  }
   template <class F>
   void guarded(F&& f) {
     try {
@@ -716,6 +769,17 @@ int64_t chunk_lo(const Run& r, int64_t j) { return std::min(r.b.n, j * r.C); }
 
 // playback queries with timers (absence states) need every row's clock on every shard
 bool need_clocks(const sg_nfa_desc& d) { return d.playback && d.n_sched > 0; }
+
+// The batch columns the query reads (d.ret_col): only these are staged, uploaded or exchanged, and only where the
+// batch brings them.
+struct NeedCols {
+  bool need[SG_MAX_COLS] = {};
+  explicit NeedCols(const sg_nfa_desc& d) {
+    for (int k = 0; k < d.n_ret; ++k) need[d.ret_col[k]] = true;
+  }
+  bool col(const sg_node_batch& b, int c) const { return need[c] && b.cols && b.cols[c]; }
+  bool nul(const sg_node_batch& b, int c) const { return need[c] && b.nulls && b.nulls[c]; }
+};
 
 // row lo + i starts a new timestamp (the first row of a thread's slice always counts: a repeated clock row at an
 // unchanged time fires nothing)
@@ -872,8 +936,8 @@ void route_chunk(Run& r, int64_t j) {
     r.rows_of[j * G + s] = o;
   }
   const int nc = d.n_cols;
-  int need[SG_MAX_COLS] = {};
-  for (int k = 0; k < d.n_ret; ++k) need[d.ret_col[k]] = 1;
+  const NeedCols needed(d);
+  const bool* need = needed.need;
   const bool stage_stream = stream != nullptr || clocks;
   nd.pool->parallel_for(T, [&](int t) {
     int64_t a, e;
@@ -925,8 +989,7 @@ sg_batch shard_batch(Run& r, int64_t j, int s, const void** cols, const uint8_t*
   sb.on_device = 0;
   sb.key_bound = r.kb_of[j * nd.G + s];
   sb.n = r.rows_of[j * nd.G + s];
-  int need[SG_MAX_COLS] = {};
-  for (int k = 0; k < d.n_ret; ++k) need[d.ret_col[k]] = 1;
+  const NeedCols nc(d);
   if (nd.G == 1) {
     const int64_t lo = chunk_lo(r, j);
     sb.base_index = r.b.base_index + (uint64_t)lo;
@@ -935,8 +998,8 @@ sg_batch shard_batch(Run& r, int64_t j, int s, const void** cols, const uint8_t*
     sb.key = nd.ddict == 1 ? nullptr : nd.keyslot[slot].as<int32_t>();   // (device mode: raw keys go up instead)
     bool nul = false;
     for (int c = 0; c < d.n_cols; ++c) {
-      cols[c] = (need[c] && r.b.cols[c]) ? (const char*)r.b.cols[c] + (size_t)sg_col_width(d.col_type[c]) * lo : nullptr;
-      nuls[c] = (need[c] && r.b.nulls && r.b.nulls[c]) ? r.b.nulls[c] + lo : nullptr;
+      cols[c] = nc.col(r.b, c) ? (const char*)r.b.cols[c] + (size_t)sg_col_width(d.col_type[c]) * lo : nullptr;
+      nuls[c] = nc.nul(r.b, c) ? r.b.nulls[c] + lo : nullptr;
       nul |= nuls[c] != nullptr;
     }
     sb.cols = cols;
@@ -950,8 +1013,8 @@ sg_batch shard_batch(Run& r, int64_t j, int s, const void** cols, const uint8_t*
   sb.key = nd.ddict == 1 ? nullptr : S.key.as<int32_t>();
   bool nul = false;
   for (int c = 0; c < d.n_cols; ++c) {
-    cols[c] = (need[c] && r.b.cols[c]) ? S.col[c].p : nullptr;
-    nuls[c] = (need[c] && r.b.nulls && r.b.nulls[c]) ? S.nul[c].as<uint8_t>() : nullptr;
+    cols[c] = nc.col(r.b, c) ? S.col[c].p : nullptr;
+    nuls[c] = nc.nul(r.b, c) ? S.nul[c].as<uint8_t>() : nullptr;
     nul |= nuls[c] != nullptr;
   }
   sb.cols = cols;
@@ -1011,6 +1074,58 @@ struct Dst {   // where delivered rows go: the caller's columns (G = 1) or the s
   int64_t M;   // ring size (rows wrap at M); G = 1: no wrap
 };
 
+Dst caller_columns(const sg_match_columns* out, int ns) {
+  Dst dst;
+  memset(&dst, 0, sizeof(dst));
+  dst.trig = out->trigger;
+  dst.ts = out->ts;
+  dst.key = out->key;
+  dst.grp = out->group;
+  for (int c = 0; c < ns; ++c) {
+    dst.col[c] = out->cols[c];
+    dst.nul[c] = out->nulls[c];
+  }
+  return dst;
+}
+
+// The columns of a delivered match, in the order every copy of them goes: trigger always, then what the push wants
+// (Want) of ts, key, group and each projected column and its null bytes.  for_each_match_col calls
+// f(offset in L, bytes per row, which column, c); match_off / match_dst find the same column in another layout or at
+// the destination.
+enum MatchCol { M_TRIG, M_TS, M_KEY, M_GRP, M_COL, M_NUL };
+template <class F>
+void for_each_match_col(const Want& w, const ColLayout& L, F f) {
+  f(L.off_trig, (size_t)8, M_TRIG, 0);
+  if (w.ts) f(L.off_ts, (size_t)8, M_TS, 0);
+  if (w.key) f(L.off_key, (size_t)4, M_KEY, 0);
+  if (w.grp) f(L.off_grp, (size_t)4, M_GRP, 0);
+  for (int c = 0; c < w.ns; ++c) {
+    if (w.col[c]) f(L.off_col[c], (size_t)L.width[c], M_COL, c);
+    if (w.nul[c]) f(L.off_nul[c], (size_t)1, M_NUL, c);
+  }
+}
+template <class Lay>   // (ColLayout or XLay: the same members)
+auto& match_off(Lay& L, MatchCol m, int c) {
+  switch (m) {
+    case M_TRIG: return L.off_trig;
+    case M_TS: return L.off_ts;
+    case M_KEY: return L.off_key;
+    case M_GRP: return L.off_grp;
+    case M_COL: return L.off_col[c];
+    default: return L.off_nul[c];
+  }
+}
+void* match_dst(const Dst& d, MatchCol m, int c) {
+  switch (m) {
+    case M_TRIG: return d.trig;
+    case M_TS: return d.ts;
+    case M_KEY: return d.key;
+    case M_GRP: return d.grp;
+    case M_COL: return d.col[c];
+    default: return d.nul[c];
+  }
+}
+
 // transpose all pending matches of h into staging slot es and copy them to dst rows [pos, pos + k) (mod M)
 void deliver(Run& r, SgHandle& h, const Dst& dst, int64_t pos, int64_t k, int es) {
   const sg_nfa_desc& d = h.desc;
@@ -1032,7 +1147,8 @@ void deliver(Run& r, SgHandle& h, const Dst& dst, int64_t pos, int64_t k, int es
   if (pos < 0 || k < 0 || (dst.M == 0 && pos + k > r.cap) || (dst.M > 0 && k > dst.M))
     throw SgError(SG_EINVAL, "internal: node delivery range [" + std::to_string(pos) + ", " + std::to_string(pos + k) +
                                  ") outside its destination");
-  auto cp = [&](void* base, size_t off, size_t width) {
+  for_each_match_col(w, L, [&](size_t off, size_t width, MatchCol m, int c) {
+    void* base = match_dst(dst, m, c);
     if (!base) return;
     const int64_t p = dst.M ? pos % dst.M : pos;
     const int64_t first = dst.M ? std::min<int64_t>(k, dst.M - p) : k;
@@ -1043,18 +1159,30 @@ void deliver(Run& r, SgHandle& h, const Dst& dst, int64_t pos, int64_t k, int es
       HIPCHK(hipMemcpyAsync(base, st + off + width * (size_t)first, width * (size_t)(k - first), hipMemcpyDeviceToHost,
                             h.eg.d2h));
     bytes += (int64_t)(width * (size_t)k);
-  };
-  cp(dst.trig, L.off_trig, 8);
-  if (w.ts) cp(dst.ts, L.off_ts, 8);
-  if (w.key) cp(dst.key, L.off_key, 4);
-  if (w.grp) cp(dst.grp, L.off_grp, 4);
-  for (int c = 0; c < w.ns; ++c) {
-    if (w.col[c]) cp(dst.col[c], L.off_col[c], (size_t)L.width[c]);
-    if (w.nul[c]) cp(dst.nul[c], L.off_nul[c], 1);
-  }
+  });
   HIPCHK(hipEventRecord(h.eg.done[es], h.eg.d2h));
   std::lock_guard<std::mutex> lk(r.mu);
   r.d2h_bytes += bytes;
+}
+
+// The device view of n rows in ingress slot sp (key_bound is the caller's to set); has_col(c) / has_nul(c): the
+// columns the rows came with.
+template <class HasCol, class HasNul>
+BatchView slot_view(const SlotPtrs& sp, int ncols, int64_t n, uint64_t base_index, bool stream, bool index,
+                    HasCol has_col, HasNul has_nul) {
+  BatchView bv;
+  memset(&bv, 0, sizeof(bv));
+  bv.n = n;
+  bv.base_index = base_index;
+  bv.ts = (const int64_t*)sp.ts;
+  bv.stream = stream ? (const int32_t*)sp.stream : nullptr;
+  bv.key = (const int32_t*)sp.key;
+  bv.index = index ? (const uint64_t*)sp.index : nullptr;
+  for (int c = 0; c < ncols; ++c) {
+    bv.cols.col[c] = has_col(c) ? sp.col[c] : nullptr;
+    bv.cols.nul[c] = has_nul(c) ? (const uint8_t*)sp.nul[c] : nullptr;
+  }
+  return bv;
 }
 
 void gpu_loop(Run& r, int s) {
@@ -1065,15 +1193,7 @@ void gpu_loop(Run& r, int s) {
     Dst dst;
     memset(&dst, 0, sizeof(dst));
     if (nd.G == 1) {
-      dst.trig = r.out->trigger;
-      dst.ts = r.out->ts;
-      dst.key = r.out->key;
-      dst.grp = r.out->group;
-      for (int c = 0; c < r.w.ns; ++c) {
-        dst.col[c] = r.out->cols[c];
-        dst.nul[c] = r.out->nulls[c];
-      }
-      dst.M = 0;
+      dst = caller_columns(r.out, r.w.ns);
     } else {
       NodeRing& R = nd.ring[s];
       dst.trig = R.trig.as<uint64_t>();
@@ -1096,16 +1216,11 @@ void gpu_loop(Run& r, int s) {
       int64_t k = 0;
       if (sb.n > 0) {
         // the device view of the slot the copy thread filled
-        BatchView bv;
-        memset(&bv, 0, sizeof(bv));
-        bv.n = sb.n;
-        bv.base_index = sb.base_index;
-        bv.key_bound = sb.key_bound;
         const SlotPtrs& sp = nd.dslot[s][ds];
-        bv.ts = (const int64_t*)sp.ts;
-        bv.stream = sb.stream ? (const int32_t*)sp.stream : nullptr;
-        bv.key = (const int32_t*)sp.key;
-        bv.index = nullptr;
+        BatchView bv = slot_view(sp, nd.desc.n_cols, sb.n, sb.base_index, sb.stream != nullptr, false,
+                                 [&](int c) { return sb.cols[c] != nullptr; },
+                                 [&](int c) { return sb.nulls && sb.nulls[c]; });
+        bv.key_bound = sb.key_bound;
         if (r.ts32_of[j]) {   // widen the 32-bit offsets into the slot's timestamp column
           hipLaunchKernelGGL(k_ts_widen, dim3((unsigned)std::min<int64_t>((sb.n + 255) / 256, 8192)), dim3(256), 0,
                              h.stream, (const int32_t*)nd.dts32[s][ds], r.ts_base_of[j], sb.n, (int64_t*)sp.ts);
@@ -1114,10 +1229,6 @@ void gpu_loop(Run& r, int s) {
         if (nd.ddict == 1) {   // dictionary-encode the chunk's raw keys on this GPU
           kd_resolve(nd.kd[s], nd.draw[s][ds], bv.stream, sb.n, (int32_t*)sp.key, h.stream, nullptr);
           bv.key_bound = (int32_t)std::max<int64_t>(1, nd.kd[s].n_keys);
-        }
-        for (int c = 0; c < nd.desc.n_cols; ++c) {
-          bv.cols.col[c] = sb.cols[c] ? sp.col[c] : nullptr;
-          bv.cols.nul[c] = (sb.nulls && sb.nulls[c]) ? (const uint8_t*)sp.nul[c] : nullptr;
         }
         sg_push_view(h, bv, sb.n);
         k = h.out.n;
@@ -1308,12 +1419,11 @@ XSpec xspec_of(const sg_node& nd, const sg_node_batch& b) {
   memset(&sp, 0, sizeof(sp));
   sp.ncols = d.n_cols;
   sp.stream = b.stream ? 1 : 0;
-  int need[SG_MAX_COLS] = {};
-  for (int k = 0; k < d.n_ret; ++k) need[d.ret_col[k]] = 1;
+  const NeedCols nc(d);
   for (int c = 0; c < d.n_cols; ++c) {
-    if (!need[c] || !b.cols || !b.cols[c]) continue;
+    if (!nc.col(b, c)) continue;
     sp.width[c] = sg_col_width(d.col_type[c]);
-    sp.nul[c] = (b.nulls && b.nulls[c]) ? 1 : 0;
+    sp.nul[c] = nc.nul(b, c) ? 1 : 0;
   }
   return sp;
 }
@@ -1332,9 +1442,10 @@ void xcopy(void* dst, int ddev, const void* src, int sdev, size_t bytes, hipStre
 }
 
 // H2D of GPU g's slice of chunk j into its ingress slot j & 1 (copy stream)
-void x_upload(Run& r, int g, int64_t j, const XSpec& sp) {
+void x_upload(Run& r, int g, int64_t j) {
   sg_node& nd = r.nd;
   XGpu& X = nd.x[g];
+  const XSpec& sp = r.xsp;
   const int p = (int)(j & 1);
   int64_t a, e;
   x_slice(r, j, g, a, e);
@@ -1359,17 +1470,11 @@ void x_upload(Run& r, int g, int64_t j, const XSpec& sp) {
   r.h2d_bytes += bytes;
 }
 
-XLay xlay(char* base, const ColLayout& L) {
+XLay xlay(char* base, const Want& w, const ColLayout& L) {   // (the columns k_xplace moves: those xwant names)
   XLay x;
+  memset(&x, 0, sizeof(x));
   x.base = base;
-  x.off_trig = L.off_trig;
-  x.off_ts = L.off_ts;
-  x.off_key = L.off_key;
-  x.off_grp = L.off_grp;
-  for (int k = 0; k < SG_MAX_SELECT; ++k) {
-    x.off_col[k] = k < L.ns ? L.off_col[k] : 0;
-    x.off_nul[k] = k < L.ns ? L.off_nul[k] : 0;
-  }
+  for_each_match_col(w, L, [&](size_t off, size_t, MatchCol m, int c) { match_off(x, m, c) = off; });
   return x;
 }
 
@@ -1387,8 +1492,43 @@ XWant xwant(const Want& w, const ColLayout& L) {
   return x;
 }
 
+// Both device ingress slots of shard s, sized for `rows` rows of the columns a chunk brings (stream / index columns
+// and has_col(c) / has_nul(c)): sg_reserve_slot only looks at which pointers of the batch are set.
+template <class HasCol, class HasNul>
+void reserve_slots(sg_node& nd, int s, int64_t rows, bool stream, bool index, HasCol has_col, HasNul has_nul) {
+  static const char dummy[1] = {0};
+  sg_batch sb;
+  memset(&sb, 0, sizeof(sb));
+  const void* cols[SG_MAX_COLS] = {};
+  const uint8_t* nuls[SG_MAX_COLS] = {};
+  sb.ts = (const int64_t*)dummy;
+  sb.key = (const int32_t*)dummy;
+  sb.index = index ? (const uint64_t*)dummy : nullptr;
+  sb.stream = stream ? (const int32_t*)dummy : nullptr;
+  bool nul = false;
+  for (int c = 0; c < nd.desc.n_cols; ++c) {
+    cols[c] = has_col(c) ? dummy : nullptr;
+    nuls[c] = has_nul(c) ? (const uint8_t*)dummy : nullptr;
+    nul |= nuls[c] != nullptr;
+  }
+  sb.cols = cols;
+  sb.nulls = nul ? nuls : nullptr;
+  for (int p = 0; p < 2; ++p) nd.dslot[s][p] = sg_reserve_slot(nd.h[s]->h, &sb, rows, p);
+}
+
+// both device slots of one shard's side column (raw keys, 32-bit timestamp offsets), reallocated for `rows` rows
+template <class T>
+void regrow_slots(T* (&slot)[2], int64_t rows) {
+  for (int p = 0; p < 2; ++p) {
+    if (slot[p]) HIPCHK(hipFree(slot[p]));
+    slot[p] = nullptr;
+    HIPCHK(hipMalloc((void**)&slot[p], (size_t)rows * sizeof(T)));
+  }
+}
+
 // device buffers of every GPU for chunks of C rows (before the pipeline's threads start)
-void x_reserve(Run& r, const XSpec& sp) {
+void x_reserve(Run& r) {
+  const XSpec& sp = r.xsp;
   sg_node& nd = r.nd;
   const int G = nd.G;
   const int64_t C = r.C, S = C / G + 1;
@@ -1426,30 +1566,9 @@ void x_reserve(Run& r, const XSpec& sp) {
     for (int p = 0; p < 2; ++p) X.hstarts[p].ensure(8 * (MAX_GPUS + 1));
     X.hbounds.ensure(8 * (MAX_GPUS + 1));
     // receive slots: a shard may get every row of a chunk
-    sg_batch sb;
-    memset(&sb, 0, sizeof(sb));
-    const void* cols[SG_MAX_COLS] = {};
-    const uint8_t* nuls[SG_MAX_COLS] = {};
-    static const char dummy[1] = {0};
-    sb.ts = (const int64_t*)dummy;
-    sb.key = (const int32_t*)dummy;
-    sb.index = (const uint64_t*)dummy;
-    sb.stream = sp.stream ? (const int32_t*)dummy : nullptr;
-    bool nul = false;
-    for (int c = 0; c < sp.ncols; ++c) {
-      cols[c] = sp.width[c] ? dummy : nullptr;
-      nuls[c] = sp.nul[c] ? (const uint8_t*)dummy : nullptr;
-      nul |= nuls[c] != nullptr;
-    }
-    sb.cols = cols;
-    sb.nulls = nul ? nuls : nullptr;
-    for (int p = 0; p < 2; ++p) nd.dslot[g][p] = sg_reserve_slot(h, &sb, C, p);
-    if (nd.draw_rows < C)
-      for (int p = 0; p < 2; ++p) {
-        if (nd.draw[g][p]) HIPCHK(hipFree(nd.draw[g][p]));
-        nd.draw[g][p] = nullptr;
-        HIPCHK(hipMalloc((void**)&nd.draw[g][p], (size_t)C * 8));
-      }
+    reserve_slots(nd, g, C, sp.stream != 0, true, [&](int c) { return sp.width[c] != 0; },
+                  [&](int c) { return sp.nul[c] != 0; });
+    if (nd.draw_rows < C) regrow_slots(nd.draw[g], C);
     HIPCHK(hipStreamSynchronize(h.stream));
     sg_egress_init(h);
     const int64_t eb = (int64_t)sg_col_layout(h.desc, std::max<int64_t>(1, std::min<int64_t>(S, r.cap))).bytes;
@@ -1470,320 +1589,355 @@ void x_merge_room(sg_node& nd, int g, int p, int64_t m, bool out_slot) {
   cap = c;
 }
 
-void x_loop(Run& r, int g, XSpec sp) {
+// ---- the exchange's stages: x_loop runs them in this order for every chunk on GPU g's thread.  A stage that waits for
+// the other GPUs returns false when the push has failed (the driver then returns at once, and run_push does the
+// stream syncs the loop skipped).
+struct XChunk {
+  int64_t j = 0;            // the chunk
+  int p = 0;                // its slot in every double buffer (j & 1)
+  int64_t a = 0, n = 0;     // GPU g's slice: rows [a, a + n) of the caller's batch
+  int64_t out_before = 0;   // matches of the chunks before this one, node-wide (the driver's)
+  int64_t ns = 0;           // x_compute: rows shard g received
+  int64_t k = 0;            // x_stage_matches: shard g's matches, in egress slot p with layout L
+  ColLayout L;
+  int64_t mg = 0, before_g = 0, chunk_total = 0;   // x_plan_merge: matches of slice g, of the slices before it, of all
+};
+
+// ---- shard of every row, counts per (block, shard), send offsets
+void x_shard(Run& r, int g, const XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  SgHandle& h = nd.h[g]->h;
+  const int G = nd.G, p = c.p;
+  const int64_t n = c.n, nblk = (n + XB_ROWS - 1) / XB_ROWS;
+  HIPCHK(hipStreamWaitEvent(h.stream, X.ev_in[p], 0));
+  uint32_t* hst = X.hstarts[p].as<uint32_t>();
+  if (n > 0) {
+    HIPCHK(hipMemsetAsync(X.bcnt.as<uint32_t>() + G * nblk, 0, 4, h.stream));
+    hipLaunchKernelGGL(k_xcount, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c.raw, X.in[p].c.stream, n,
+                       (uint32_t)G, X.shard.as<uint8_t>(), X.bcnt.as<uint32_t>(), (uint32_t)nblk);
+    HIPCHK(hipGetLastError());
+    size_t tb = X.scan_tmp.bytes;
+    HIPCHK(rocprim::exclusive_scan(X.scan_tmp.p, tb, X.bcnt.as<uint32_t>(), X.boff.as<uint32_t>(), (uint32_t)0,
+                                   (size_t)(G * nblk + 1), rocprim::plus<uint32_t>(), h.stream));
+    hipLaunchKernelGGL(k_xstarts, dim3(1), dim3(64), 0, h.stream, X.boff.as<uint32_t>(), (uint32_t)nblk, (uint32_t)G,
+                       X.starts.as<uint32_t>());
+    HIPCHK(hipMemcpyAsync(hst, X.starts.p, 4 * (size_t)(G + 1), hipMemcpyDeviceToHost, h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+    hipLaunchKernelGGL(k_xscatter, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c, X.send[p].c, r.xsp, n,
+                       r.b.base_index + (uint64_t)c.a, X.shard.as<uint8_t>(), X.boff.as<uint32_t>(), (uint32_t)nblk,
+                       (uint32_t)G);
+    HIPCHK(hipGetLastError());
+  } else {
+    for (int s = 0; s <= G; ++s) hst[s] = 0;
+  }
+  HIPCHK(hipEventRecord(X.ev_scat[p], h.stream));
+  r.x_pass(X_COUNTED, g, c.j, [&] {
+    int64_t* st = r.x_row(r.xst, c.j, g);
+    for (int s = 0; s <= G; ++s) st[s] = hst[s];
+  });
+}
+
+// ---- rows to their shards: piece (g -> s) lands after the pieces of slices 0 .. g-1
+bool x_send_rows(Run& r, int g, const XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  const XSpec& sp = r.xsp;
+  const int G = nd.G, p = c.p;
+  const int64_t j = c.j;
+  if (!r.wait([&] {
+        if (!r.x_past(X_COUNTED, j)) return false;
+        if (j < 2) return true;
+        for (int s = 0; s < G; ++s)
+          if (r.xstep[X_USED][s] < j - 1) return false;   // shard s consumed chunk j - 2 from its receive slot p
+        return true;
+      }))
+    return false;
+  HIPCHK(hipStreamWaitEvent(X.xs, X.ev_scat[p], 0));
+  for (int s = 0; s < G; ++s) {
+    const int64_t cnt = r.x_cnt(r.xst, j, g, s);
+    if (!cnt) continue;
+    int64_t ro = 0;
+    for (int q = 0; q < g; ++q) ro += r.x_cnt(r.xst, j, q, s);
+    const int64_t so = r.x_row(r.xst, j, g)[s];
+    if (j >= 2) HIPCHK(hipStreamWaitEvent(X.xs, nd.x[s].ev_rfree[p], 0));
+    const SlotPtrs& rs = nd.dslot[s][p];
+    const XCols& sc = X.send[p].c;
+    const int ds = nd.dev[s], dg = nd.dev[g];
+    xcopy((int64_t*)rs.ts + ro, ds, sc.ts + so, dg, 8 * (size_t)cnt, X.xs);
+    xcopy(nd.draw[s][p] + ro, ds, sc.raw + so, dg, 8 * (size_t)cnt, X.xs);
+    xcopy((uint64_t*)rs.index + ro, ds, sc.gidx + so, dg, 8 * (size_t)cnt, X.xs);
+    if (sp.stream) xcopy((int32_t*)rs.stream + ro, ds, sc.stream + so, dg, 4 * (size_t)cnt, X.xs);
+    for (int k = 0; k < sp.ncols; ++k) {
+      if (sp.width[k])
+        xcopy((char*)rs.col[k] + (size_t)sp.width[k] * ro, ds, (const char*)sc.col[k] + (size_t)sp.width[k] * so, dg,
+              (size_t)sp.width[k] * cnt, X.xs);
+      if (sp.nul[k]) xcopy((uint8_t*)rs.nul[k] + ro, ds, sc.nul[k] + so, dg, (size_t)cnt, X.xs);
+    }
+  }
+  HIPCHK(hipEventRecord(X.ev_sent[p], X.xs));
+  r.x_pass(X_SENT, g, j);
+  return true;
+}
+
+// ---- shard g: its rows of chunk j, arrival order, global indices as triggers
+bool x_compute(Run& r, int g, XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  SgHandle& h = nd.h[g]->h;
+  const XSpec& sp = r.xsp;
+  const int G = nd.G, p = c.p;
+  const int64_t j = c.j;
+  if (!r.x_wait(X_SENT, j)) return false;
+  c.ns = 0;
+  for (int q = 0; q < G; ++q) {
+    c.ns += r.x_cnt(r.xst, j, q, g);
+    HIPCHK(hipStreamWaitEvent(h.stream, nd.x[q].ev_sent[p], 0));
+  }
+  const SlotPtrs& sl = nd.dslot[g][p];
+  const int64_t ns = c.ns, kbefore = nd.kd[g].n_keys;
+  int64_t mnew = 0;
+  if (ns > 0) {
+    BatchView bv = slot_view(sl, sp.ncols, ns, 0, sp.stream != 0, true, [&](int k) { return sp.width[k] != 0; },
+                             [&](int k) { return sp.nul[k] != 0; });
+    mnew = kd_resolve(nd.kd[g], nd.draw[g][p], bv.stream, ns, (int32_t*)sl.key, h.stream, nullptr);
+    if (r.w.key && mnew > 0) {   // global first rows of the new keys (node-wide first-seen ids)
+      X.nfg.ensure(8 * (size_t)mnew);
+      X.hnf.ensure(8 * (size_t)mnew);
+      hipLaunchKernelGGL(k_xgather_u64, dim3((unsigned)((mnew + 255) / 256)), dim3(256), 0, h.stream,
+                         (const uint64_t*)sl.index, nd.kd[g].sfirst, mnew, X.nfg.as<uint64_t>());
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(X.hnf.p, X.nfg.p, 8 * (size_t)mnew, hipMemcpyDeviceToHost, h.stream));
+      HIPCHK(hipStreamSynchronize(h.stream));
+    }
+    bv.key_bound = (int32_t)std::max<int64_t>(1, nd.kd[g].n_keys);
+    sg_push_view(h, bv, ns);
+  }
+  HIPCHK(hipEventRecord(X.ev_rfree[p], h.stream));
+  r.x_pass(X_USED, g, j, [&] {
+    nd.local_rows[g] += ns;
+    if (r.w.key) {
+      r.xnf[(size_t)(j * G + g)].assign(X.hnf.as<uint64_t>(), X.hnf.as<uint64_t>() + (mnew > 0 ? mnew : 0));
+      r.xkbase[(size_t)(j * G + g)] = kbefore;
+    }
+  });
+  return true;
+}
+
+// ---- node-wide first-seen key ids (only when the caller wants keys): the shards' new keys interleaved by their first
+// global row; GPU 0's thread assigns them for everyone, then every GPU appends its own to its device l2g
+bool x_assign_ids(Run& r, int g, const XChunk& c) {
   sg_node& nd = r.nd;
   XGpu& X = nd.x[g];
   SgHandle& h = nd.h[g]->h;
   const int G = nd.G;
-  const sg_nfa_desc& d = nd.desc;
-  const Want& w = r.w;
-  auto all_gt = [&](const int64_t* v, int64_t j) {
-    for (int q = 0; q < G; ++q)
-      if (v[q] <= j) return false;
-    return true;
-  };
-  r.guarded([&] {
-    HIPCHK(hipSetDevice(nd.dev[g]));
-    int64_t out_before = 0;   // matches of the chunks before this one, node-wide
-    for (int64_t j = 0; j < r.nch; ++j) {
-      const double t0 = now_ms();
-      const int p = (int)(j & 1);
-      if (j == 0) x_upload(r, g, 0, sp);
-      if (j + 1 < r.nch) x_upload(r, g, j + 1, sp);   // (slot (j + 1) & 1 held chunk j - 1, scattered already)
-      int64_t a, e;
-      x_slice(r, j, g, a, e);
-      const int64_t n = e - a;
-      const int64_t nblk = (n + XB_ROWS - 1) / XB_ROWS;
-      // ---- shard of every row, counts per (block, shard), send offsets
-      HIPCHK(hipStreamWaitEvent(h.stream, X.ev_in[p], 0));
-      uint32_t* hst = X.hstarts[p].as<uint32_t>();
-      if (n > 0) {
-        HIPCHK(hipMemsetAsync(X.bcnt.as<uint32_t>() + G * nblk, 0, 4, h.stream));
-        hipLaunchKernelGGL(k_xcount, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c.raw, X.in[p].c.stream, n,
-                           (uint32_t)G, X.shard.as<uint8_t>(), X.bcnt.as<uint32_t>(), (uint32_t)nblk);
-        HIPCHK(hipGetLastError());
-        size_t tb = X.scan_tmp.bytes;
-        HIPCHK(rocprim::exclusive_scan(X.scan_tmp.p, tb, X.bcnt.as<uint32_t>(), X.boff.as<uint32_t>(), (uint32_t)0,
-                                       (size_t)(G * nblk + 1), rocprim::plus<uint32_t>(), h.stream));
-        hipLaunchKernelGGL(k_xstarts, dim3(1), dim3(64), 0, h.stream, X.boff.as<uint32_t>(), (uint32_t)nblk, (uint32_t)G,
-                           X.starts.as<uint32_t>());
-        HIPCHK(hipMemcpyAsync(hst, X.starts.p, 4 * (size_t)(G + 1), hipMemcpyDeviceToHost, h.stream));
-        HIPCHK(hipStreamSynchronize(h.stream));
-        hipLaunchKernelGGL(k_xscatter, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c, X.send[p].c, sp, n,
-                           r.b.base_index + (uint64_t)a, X.shard.as<uint8_t>(), X.boff.as<uint32_t>(), (uint32_t)nblk,
-                           (uint32_t)G);
-        HIPCHK(hipGetLastError());
-      } else {
-        for (int s = 0; s <= G; ++s) hst[s] = 0;
-      }
-      HIPCHK(hipEventRecord(X.ev_scat[p], h.stream));
-      r.publish([&] {
-        for (int s = 0; s <= G; ++s) r.xst[(size_t)(j * G + g) * (G + 1) + s] = hst[s];
-        r.xcounted[g] = j + 1;
-      });
-      // ---- rows to their shards: piece (g -> s) lands after the pieces of slices 0 .. g-1
-      if (!r.wait([&] {
-            if (!all_gt(r.xcounted, j)) return false;
-            if (j < 2) return true;
-            for (int s = 0; s < G; ++s)
-              if (r.xused[s] < j - 1) return false;   // shard s consumed chunk j - 2 from its receive slot p
-            return true;
-          }))
-        return;
-      auto cnt_of = [&](int src, int s) {
-        const int64_t* q = &r.xst[(size_t)(j * G + src) * (G + 1)];
-        return q[s + 1] - q[s];
-      };
-      HIPCHK(hipStreamWaitEvent(X.xs, X.ev_scat[p], 0));
-      for (int s = 0; s < G; ++s) {
-        const int64_t c = cnt_of(g, s);
-        if (!c) continue;
-        int64_t ro = 0;
-        for (int q = 0; q < g; ++q) ro += cnt_of(q, s);
-        const int64_t so = r.xst[(size_t)(j * G + g) * (G + 1) + s];
-        if (j >= 2) HIPCHK(hipStreamWaitEvent(X.xs, nd.x[s].ev_rfree[p], 0));
-        const SlotPtrs& rs = nd.dslot[s][p];
-        const XCols& sc = X.send[p].c;
-        const int ds = nd.dev[s], dg = nd.dev[g];
-        xcopy((int64_t*)rs.ts + ro, ds, sc.ts + so, dg, 8 * (size_t)c, X.xs);
-        xcopy(nd.draw[s][p] + ro, ds, sc.raw + so, dg, 8 * (size_t)c, X.xs);
-        xcopy((uint64_t*)rs.index + ro, ds, sc.gidx + so, dg, 8 * (size_t)c, X.xs);
-        if (sp.stream) xcopy((int32_t*)rs.stream + ro, ds, sc.stream + so, dg, 4 * (size_t)c, X.xs);
-        for (int k = 0; k < sp.ncols; ++k) {
-          if (sp.width[k])
-            xcopy((char*)rs.col[k] + (size_t)sp.width[k] * ro, ds, (const char*)sc.col[k] + (size_t)sp.width[k] * so, dg,
-                  (size_t)sp.width[k] * c, X.xs);
-          if (sp.nul[k]) xcopy((uint8_t*)rs.nul[k] + ro, ds, sc.nul[k] + so, dg, (size_t)c, X.xs);
-        }
-      }
-      HIPCHK(hipEventRecord(X.ev_sent[p], X.xs));
-      r.publish([&] { r.xsent[g] = j + 1; });
-      // ---- shard g: its rows of chunk j, arrival order, global indices as triggers
-      if (!r.wait([&] { return all_gt(r.xsent, j); })) return;
-      int64_t ns = 0;
-      for (int q = 0; q < G; ++q) {
-        ns += cnt_of(q, g);
-        HIPCHK(hipStreamWaitEvent(h.stream, nd.x[q].ev_sent[p], 0));
-      }
-      const SlotPtrs& sl = nd.dslot[g][p];
-      int64_t kbefore = nd.kd[g].n_keys, mnew = 0;
-      if (ns > 0) {
-        mnew = kd_resolve(nd.kd[g], nd.draw[g][p], sp.stream ? (const int32_t*)sl.stream : nullptr, ns,
-                          (int32_t*)sl.key, h.stream, nullptr);
-        if (w.key && mnew > 0) {   // global first rows of the new keys (node-wide first-seen ids)
-          X.nfg.ensure(8 * (size_t)mnew);
-          X.hnf.ensure(8 * (size_t)mnew);
-          hipLaunchKernelGGL(k_xgather_u64, dim3((unsigned)((mnew + 255) / 256)), dim3(256), 0, h.stream,
-                             (const uint64_t*)sl.index, nd.kd[g].sfirst, mnew, X.nfg.as<uint64_t>());
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(X.hnf.p, X.nfg.p, 8 * (size_t)mnew, hipMemcpyDeviceToHost, h.stream));
-          HIPCHK(hipStreamSynchronize(h.stream));
-        }
-        BatchView bv;
-        memset(&bv, 0, sizeof(bv));
-        bv.n = ns;
-        bv.base_index = 0;
-        bv.key_bound = (int32_t)std::max<int64_t>(1, nd.kd[g].n_keys);
-        bv.ts = (const int64_t*)sl.ts;
-        bv.stream = sp.stream ? (const int32_t*)sl.stream : nullptr;
-        bv.key = (const int32_t*)sl.key;
-        bv.index = (const uint64_t*)sl.index;
-        for (int k = 0; k < sp.ncols; ++k) {
-          bv.cols.col[k] = sp.width[k] ? sl.col[k] : nullptr;
-          bv.cols.nul[k] = sp.nul[k] ? (const uint8_t*)sl.nul[k] : nullptr;
-        }
-        sg_push_view(h, bv, ns);
-      }
-      HIPCHK(hipEventRecord(X.ev_rfree[p], h.stream));
-      r.publish([&] {
-        r.xused[g] = j + 1;
-        nd.local_rows[g] += ns;
-        if (w.key) {
-          r.xnf[(size_t)(j * G + g)].assign(X.hnf.as<uint64_t>(), X.hnf.as<uint64_t>() + (mnew > 0 ? mnew : 0));
-          r.xkbase[(size_t)(j * G + g)] = kbefore;
-          r.xnfp[g] = j + 1;
-        }
-      });
-      // ---- node-wide first-seen key ids (only when the caller wants keys): the shards' new keys interleaved by
-      // their first global row; GPU 0's thread assigns them for everyone
-      if (w.key) {
-        if (g == 0) {
-          if (!r.wait([&] { return all_gt(r.xnfp, j); })) return;
-          int64_t cur[MAX_GPUS] = {}, m[MAX_GPUS];
-          for (int s = 0; s < G; ++s) {
-            m[s] = (int64_t)r.xnf[(size_t)(j * G + s)].size();
-            if (m[s] > 0) nd.l2g[s].resize((size_t)(r.xkbase[(size_t)(j * G + s)] + m[s]));
-          }
-          while (true) {
-            int best = -1;
-            for (int s = 0; s < G; ++s)
-              if (cur[s] < m[s] && (best < 0 || r.xnf[(size_t)(j * G + s)][cur[s]] < r.xnf[(size_t)(j * G + best)][cur[best]]))
-                best = s;
-            if (best < 0) break;
-            nd.l2g[best][(size_t)(r.xkbase[(size_t)(j * G + best)] + cur[best])] = (int32_t)nd.g_keys++;
-            ++cur[best];
-          }
-          r.publish([&] { r.xids = j + 1; });
-        }
-        if (!r.wait([&] { return r.xids > j; })) return;
-        const int64_t nk = (int64_t)nd.l2g[g].size();
-        if (nk > X.l2g_n) {
-          if ((size_t)nk * 4 > X.l2g.bytes) {
-            HIPCHK(hipStreamSynchronize(h.stream));
-            XBuf nb;
-            nb.ensure((size_t)(nk + nk / 2 + 1024) * 4);
-            if (X.l2g_n) HIPCHK(hipMemcpy(nb.p, X.l2g.p, 4 * (size_t)X.l2g_n, hipMemcpyDeviceToDevice));
-            X.l2g.release();
-            X.l2g = nb;
-            nb.p = nullptr;
-          }
-          HIPCHK(hipMemcpyAsync(X.l2g.as<int32_t>() + X.l2g_n, nd.l2g[g].data() + X.l2g_n, 4 * (size_t)(nk - X.l2g_n),
-                                hipMemcpyHostToDevice, h.stream));
-          HIPCHK(hipStreamSynchronize(h.stream));
-          X.l2g_n = nk;
-        }
-      }
-      // ---- its matches -> SoA columns in egress slot p, cut by trigger slice
-      const int64_t k = h.out.n;
-      ColLayout L = sg_col_layout(d, std::max<int64_t>(k, 1));
-      int64_t* hb = X.hbounds.as<int64_t>();
-      if (k > 0) {
-        sg_stage_reserve(h, p, (int64_t)L.bytes);
-        HIPCHK(hipStreamWaitEvent(h.stream, h.eg.done[p], 0));
-        sg_launch_to_columns(k, h.out.rec, h.out.stride, L, h.eg.stage[p], h.stream);
-        h.out.n = 0;
-        if (w.key)
-          hipLaunchKernelGGL(k_xmapkeys, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h.stream,
-                             (int32_t*)(h.eg.stage[p] + L.off_key), k, X.l2g.as<int32_t>());
-        XSlices xs;
-        for (int q = 0; q <= G; ++q) {
-          int64_t qa, qe;
-          x_slice(r, j, q < G ? q : G - 1, qa, qe);
-          xs.lo[q] = r.b.base_index + (uint64_t)(q < G ? qa : qe);
-        }
-        hipLaunchKernelGGL(k_xbounds, dim3(1), dim3(64), 0, h.stream, (const uint64_t*)(h.eg.stage[p] + L.off_trig), k, xs,
-                           (uint32_t)G, X.bounds.as<int64_t>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(hb, X.bounds.p, 8 * (size_t)(G + 1), hipMemcpyDeviceToHost, h.stream));
-        HIPCHK(hipEventRecord(h.eg.ready[p], h.stream));
-        HIPCHK(hipStreamSynchronize(h.stream));
-      } else {
-        for (int q = 0; q <= G; ++q) hb[q] = 0;
-      }
-      r.publish([&] {
-        for (int q = 0; q <= G; ++q) r.xpc[(size_t)(j * G + g) * (G + 1) + q] = hb[q];
-        r.xpieced[g] = j + 1;
-      });
-      auto piece = [&](int s, int q) {
-        const int64_t* b2 = &r.xpc[(size_t)(j * G + s) * (G + 1)];
-        return b2[q + 1] - b2[q];
-      };
-      // ---- slice owner g: room for the matches of its triggers
-      if (!r.wait([&] { return all_gt(r.xpieced, j); })) return;
-      int64_t mg = 0, chunk_total = 0, before_g = 0;
-      for (int s = 0; s < G; ++s) mg += piece(s, g);
-      for (int q = 0; q < G; ++q)
-        for (int s = 0; s < G; ++s) {
-          chunk_total += piece(s, q);
-          if (q < g) before_g += piece(s, q);
-        }
-      if (out_before + chunk_total > r.cap) throw SgError(SG_ECAPACITY, "node: more matches than the output capacity");
-      if (mg > 0) x_merge_room(nd, g, p, mg, false);
-      r.publish([&] { r.xmready[g] = j + 1; });
-      // ---- shard g: piece (g -> q) into owner q's merge input after the pieces of shards 0 .. g-1
-      if (!r.wait([&] { return all_gt(r.xmready, j); })) return;
-      if (k > 0) {
-        HIPCHK(hipStreamWaitEvent(X.xs, h.eg.ready[p], 0));
-        for (int q = 0; q < G; ++q) {
-          const int64_t c = piece(g, q);
-          if (!c) continue;
-          int64_t ro = 0;
-          for (int s = 0; s < g; ++s) ro += piece(s, q);
-          XGpu& Q = nd.x[q];
-          if (j >= 2) HIPCHK(hipStreamWaitEvent(X.xs, Q.ev_mfree[p], 0));   // owner q merged chunk j - 2
-          const ColLayout Lq = sg_col_layout(d, Q.min_cap[p]);
-          char* dst = Q.min[p].as<char>();
-          const char* src = h.eg.stage[p];
-          const int64_t sr = r.xpc[(size_t)(j * G + g) * (G + 1) + q];
-          const int dq = nd.dev[q], dg = nd.dev[g];
-          auto col = [&](size_t doff, size_t soff, size_t wd) {
-            xcopy(dst + doff + wd * (size_t)ro, dq, src + soff + wd * (size_t)sr, dg, wd * (size_t)c, X.xs);
-          };
-          col(Lq.off_trig, L.off_trig, 8);
-          if (w.ts) col(Lq.off_ts, L.off_ts, 8);
-          if (w.key) col(Lq.off_key, L.off_key, 4);
-          if (w.grp) col(Lq.off_grp, L.off_grp, 4);
-          for (int c2 = 0; c2 < L.ns; ++c2) {
-            if (w.col[c2]) col(Lq.off_col[c2], L.off_col[c2], (size_t)L.width[c2]);
-            if (w.nul[c2]) col(Lq.off_nul[c2], L.off_nul[c2], 1);
-          }
-        }
-        HIPCHK(hipEventRecord(h.eg.done[p], X.xs));
-      }
-      HIPCHK(hipEventRecord(X.ev_osent[p], X.xs));
-      r.publish([&] { r.xosent[g] = j + 1; });
-      // ---- owner g: merge the G runs by trigger, then straight into the caller's columns
-      if (!r.wait([&] { return all_gt(r.xosent, j); })) return;
-      for (int q = 0; q < G; ++q) HIPCHK(hipStreamWaitEvent(h.stream, nd.x[q].ev_osent[p], 0));
-      const int64_t o0 = out_before + before_g;
-      if (mg > 0) {
-        x_merge_room(nd, g, p, mg, true);
-        int64_t sa, se;
-        x_slice(r, j, g, sa, se);
-        const int64_t nsl = se - sa;
-        const uint64_t slo = r.b.base_index + (uint64_t)sa;
-        XRuns runs;
-        runs.off[0] = 0;
-        for (int s = 0; s < G; ++s) runs.off[s + 1] = runs.off[s] + piece(s, g);
-        HIPCHK(hipMemsetAsync(X.mcnt.p, 0, 4 * (size_t)(nsl + 1), h.stream));
-        const ColLayout Li = sg_col_layout(d, X.min_cap[p]), Lo = sg_col_layout(d, X.mo_cap[p]);
-        const XLay li = xlay(X.min[p].as<char>(), Li), lo = xlay(X.mo[p].as<char>(), Lo);
-        hipLaunchKernelGGL(k_xmark, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream,
-                           (const uint64_t*)(li.base + li.off_trig), mg, runs, (uint32_t)G, slo, X.mcnt.as<uint32_t>(),
-                           X.mseg.as<uint32_t>());
-        HIPCHK(hipGetLastError());
-        size_t tb = X.mscan_tmp.bytes;
-        HIPCHK(rocprim::exclusive_scan(X.mscan_tmp.p, tb, X.mcnt.as<uint32_t>(), X.moff.as<uint32_t>(), (uint32_t)0,
-                                       (size_t)(nsl + 1), rocprim::plus<uint32_t>(), h.stream));
-        HIPCHK(hipStreamWaitEvent(h.stream, X.ev_d2h[p], 0));   // the output slot's last copies are done
-        hipLaunchKernelGGL(k_xplace, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream, li, mg, slo,
-                           X.moff.as<uint32_t>(), X.mseg.as<uint32_t>(), lo, xwant(w, Lo));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(X.ev_mfree[p], h.stream));
-        HIPCHK(hipStreamWaitEvent(h.eg.d2h, X.ev_mfree[p], 0));
-        int64_t bytes = 0;
-        if (o0 < 0 || o0 + mg > r.cap)
-          throw SgError(SG_EINVAL, "internal: exchange delivery rows [" + std::to_string(o0) + ", " +
-                                       std::to_string(o0 + mg) + ") beyond the output capacity");
-        auto down = [&](void* dst, size_t off, size_t wd) {
-          if (!dst) return;
-          HIPCHK(hipMemcpyAsync((char*)dst + wd * (size_t)o0, lo.base + off, wd * (size_t)mg, hipMemcpyDeviceToHost,
-                                h.eg.d2h));
-          bytes += (int64_t)(wd * (size_t)mg);
-        };
-        down(r.out->trigger, Lo.off_trig, 8);
-        if (w.ts) down(r.out->ts, Lo.off_ts, 8);
-        if (w.key) down(r.out->key, Lo.off_key, 4);
-        if (w.grp) down(r.out->group, Lo.off_grp, 4);
-        for (int c2 = 0; c2 < Lo.ns; ++c2) {
-          if (w.col[c2]) down(r.out->cols[c2], Lo.off_col[c2], (size_t)Lo.width[c2]);
-          if (w.nul[c2]) down(r.out->nulls[c2], Lo.off_nul[c2], 1);
-        }
-        HIPCHK(hipEventRecord(X.ev_d2h[p], h.eg.d2h));
-        std::lock_guard<std::mutex> lk(r.mu);
-        r.d2h_bytes += bytes;
-      } else {
-        HIPCHK(hipEventRecord(X.ev_mfree[p], h.stream));
-      }
-      out_before += chunk_total;
-      r.publish([&] {
-        r.t_gpu[g] += now_ms() - t0;
-        if (g == 0) r.out_rows = out_before;
+  const int64_t j = c.j;
+  if (g == 0) {
+    if (!r.x_wait(X_USED, j)) return false;   // every shard's new keys of chunk j are in xnf / xkbase
+    int64_t cur[MAX_GPUS] = {}, m[MAX_GPUS];
+    const std::vector<uint64_t>* nf = &r.xnf[(size_t)(j * G)];
+    const int64_t* kbase = &r.xkbase[(size_t)(j * G)];
+    for (int s = 0; s < G; ++s) {
+      m[s] = (int64_t)nf[s].size();
+      if (m[s] > 0) nd.l2g[s].resize((size_t)(kbase[s] + m[s]));
+    }
+    while (true) {
+      int best = -1;
+      for (int s = 0; s < G; ++s)
+        if (cur[s] < m[s] && (best < 0 || nf[s][cur[s]] < nf[best][cur[best]])) best = s;
+      if (best < 0) break;
+      nd.l2g[best][(size_t)(kbase[best] + cur[best])] = (int32_t)nd.g_keys++;
+      ++cur[best];
+    }
+    r.publish([&] { r.xids = j + 1; });
+  }
+  if (!r.wait([&] { return r.xids > j; })) return false;   // (one counter: GPU 0's)
+  const int64_t nk = (int64_t)nd.l2g[g].size();
+  if (nk > X.l2g_n) {
+    X.l2g_reserve(nk, h.stream);
+    HIPCHK(hipMemcpyAsync(X.l2g.as<int32_t>() + X.l2g_n, nd.l2g[g].data() + X.l2g_n, 4 * (size_t)(nk - X.l2g_n),
+                          hipMemcpyHostToDevice, h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+    X.l2g_n = nk;
+  }
+  return true;
+}
+
+// ---- its matches -> SoA columns in egress slot p, cut by trigger slice
+void x_stage_matches(Run& r, int g, XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  SgHandle& h = nd.h[g]->h;
+  const int G = nd.G, p = c.p;
+  const int64_t j = c.j, k = h.out.n;
+  c.k = k;
+  c.L = sg_col_layout(nd.desc, std::max<int64_t>(k, 1));
+  const ColLayout& L = c.L;
+  int64_t* hb = X.hbounds.as<int64_t>();
+  if (k > 0) {
+    sg_stage_reserve(h, p, (int64_t)L.bytes);
+    HIPCHK(hipStreamWaitEvent(h.stream, h.eg.done[p], 0));
+    sg_launch_to_columns(k, h.out.rec, h.out.stride, L, h.eg.stage[p], h.stream);
+    h.out.n = 0;
+    if (r.w.key)
+      hipLaunchKernelGGL(k_xmapkeys, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, h.stream,
+                         (int32_t*)(h.eg.stage[p] + L.off_key), k, X.l2g.as<int32_t>());
+    XSlices xs;
+    for (int q = 0; q <= G; ++q) {
+      int64_t qa, qe;
+      x_slice(r, j, q < G ? q : G - 1, qa, qe);
+      xs.lo[q] = r.b.base_index + (uint64_t)(q < G ? qa : qe);
+    }
+    hipLaunchKernelGGL(k_xbounds, dim3(1), dim3(64), 0, h.stream, (const uint64_t*)(h.eg.stage[p] + L.off_trig), k, xs,
+                       (uint32_t)G, X.bounds.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hb, X.bounds.p, 8 * (size_t)(G + 1), hipMemcpyDeviceToHost, h.stream));
+    HIPCHK(hipEventRecord(h.eg.ready[p], h.stream));
+    HIPCHK(hipStreamSynchronize(h.stream));
+  } else {
+    for (int q = 0; q <= G; ++q) hb[q] = 0;
+  }
+  r.x_pass(X_PIECED, g, j, [&] {
+    int64_t* pc = r.x_row(r.xpc, j, g);
+    for (int q = 0; q <= G; ++q) pc[q] = hb[q];
+  });
+}
+
+// ---- slice owner g: room for the matches of its triggers
+bool x_plan_merge(Run& r, int g, XChunk& c) {
+  sg_node& nd = r.nd;
+  const int G = nd.G;
+  const int64_t j = c.j;
+  if (!r.x_wait(X_PIECED, j)) return false;
+  c.mg = c.chunk_total = c.before_g = 0;
+  for (int s = 0; s < G; ++s) c.mg += r.x_cnt(r.xpc, j, s, g);
+  for (int q = 0; q < G; ++q)
+    for (int s = 0; s < G; ++s) {
+      c.chunk_total += r.x_cnt(r.xpc, j, s, q);
+      if (q < g) c.before_g += r.x_cnt(r.xpc, j, s, q);
+    }
+  if (c.out_before + c.chunk_total > r.cap) throw SgError(SG_ECAPACITY, "node: more matches than the output capacity");
+  if (c.mg > 0) x_merge_room(nd, g, c.p, c.mg, false);
+  r.x_pass(X_MREADY, g, j);
+  return true;
+}
+
+// ---- shard g: piece (g -> q) into owner q's merge input after the pieces of shards 0 .. g-1
+bool x_send_matches(Run& r, int g, const XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  SgHandle& h = nd.h[g]->h;
+  const int G = nd.G, p = c.p;
+  const int64_t j = c.j;
+  if (!r.x_wait(X_MREADY, j)) return false;
+  if (c.k > 0) {
+    HIPCHK(hipStreamWaitEvent(X.xs, h.eg.ready[p], 0));
+    for (int q = 0; q < G; ++q) {
+      const int64_t cnt = r.x_cnt(r.xpc, j, g, q);
+      if (!cnt) continue;
+      int64_t ro = 0;
+      for (int s = 0; s < g; ++s) ro += r.x_cnt(r.xpc, j, s, q);
+      XGpu& Q = nd.x[q];
+      if (j >= 2) HIPCHK(hipStreamWaitEvent(X.xs, Q.ev_mfree[p], 0));   // owner q merged chunk j - 2
+      const ColLayout Lq = sg_col_layout(nd.desc, Q.min_cap[p]);
+      char* dst = Q.min[p].as<char>();
+      const char* src = h.eg.stage[p];
+      const int64_t sr = r.x_row(r.xpc, j, g)[q];
+      const int dq = nd.dev[q], dg = nd.dev[g];
+      for_each_match_col(r.w, c.L, [&](size_t soff, size_t wd, MatchCol m, int cc) {
+        xcopy(dst + match_off(Lq, m, cc) + wd * (size_t)ro, dq, src + soff + wd * (size_t)sr, dg, wd * (size_t)cnt, X.xs);
       });
     }
-    HIPCHK(hipStreamSynchronize(h.stream));
-    HIPCHK(hipStreamSynchronize(X.xs));
-    HIPCHK(hipStreamSynchronize(h.eg.d2h));
+    HIPCHK(hipEventRecord(h.eg.done[p], X.xs));
+  }
+  HIPCHK(hipEventRecord(X.ev_osent[p], X.xs));
+  r.x_pass(X_OSENT, g, j);
+  return true;
+}
+
+// ---- owner g: merge the G runs by trigger, then straight into the caller's columns
+bool x_merge_deliver(Run& r, int g, const XChunk& c) {
+  sg_node& nd = r.nd;
+  XGpu& X = nd.x[g];
+  SgHandle& h = nd.h[g]->h;
+  const int G = nd.G, p = c.p;
+  const int64_t j = c.j, mg = c.mg;
+  if (!r.x_wait(X_OSENT, j)) return false;
+  for (int q = 0; q < G; ++q) HIPCHK(hipStreamWaitEvent(h.stream, nd.x[q].ev_osent[p], 0));
+  const int64_t o0 = c.out_before + c.before_g;
+  if (mg == 0) {
+    HIPCHK(hipEventRecord(X.ev_mfree[p], h.stream));
+    return true;
+  }
+  x_merge_room(nd, g, p, mg, true);
+  const uint64_t slo = r.b.base_index + (uint64_t)c.a;
+  XRuns runs;
+  runs.off[0] = 0;
+  for (int s = 0; s < G; ++s) runs.off[s + 1] = runs.off[s] + r.x_cnt(r.xpc, j, s, g);
+  HIPCHK(hipMemsetAsync(X.mcnt.p, 0, 4 * (size_t)(c.n + 1), h.stream));
+  const ColLayout Li = sg_col_layout(nd.desc, X.min_cap[p]), Lo = sg_col_layout(nd.desc, X.mo_cap[p]);
+  const XLay li = xlay(X.min[p].as<char>(), r.w, Li), lo = xlay(X.mo[p].as<char>(), r.w, Lo);
+  hipLaunchKernelGGL(k_xmark, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream,
+                     (const uint64_t*)(li.base + li.off_trig), mg, runs, (uint32_t)G, slo, X.mcnt.as<uint32_t>(),
+                     X.mseg.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  size_t tb = X.mscan_tmp.bytes;
+  HIPCHK(rocprim::exclusive_scan(X.mscan_tmp.p, tb, X.mcnt.as<uint32_t>(), X.moff.as<uint32_t>(), (uint32_t)0,
+                                 (size_t)(c.n + 1), rocprim::plus<uint32_t>(), h.stream));
+  HIPCHK(hipStreamWaitEvent(h.stream, X.ev_d2h[p], 0));   // the output slot's last copies are done
+  hipLaunchKernelGGL(k_xplace, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream, li, mg, slo,
+                     X.moff.as<uint32_t>(), X.mseg.as<uint32_t>(), lo, xwant(r.w, Lo));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(X.ev_mfree[p], h.stream));
+  HIPCHK(hipStreamWaitEvent(h.eg.d2h, X.ev_mfree[p], 0));
+  int64_t bytes = 0;
+  if (o0 < 0 || o0 + mg > r.cap)
+    throw SgError(SG_EINVAL, "internal: exchange delivery rows [" + std::to_string(o0) + ", " +
+                                 std::to_string(o0 + mg) + ") beyond the output capacity");
+  const Dst out = caller_columns(r.out, r.w.ns);
+  for_each_match_col(r.w, Lo, [&](size_t off, size_t wd, MatchCol m, int cc) {
+    void* dst = match_dst(out, m, cc);
+    if (!dst) return;
+    HIPCHK(hipMemcpyAsync((char*)dst + wd * (size_t)o0, lo.base + off, wd * (size_t)mg, hipMemcpyDeviceToHost, h.eg.d2h));
+    bytes += (int64_t)(wd * (size_t)mg);
+  });
+  HIPCHK(hipEventRecord(X.ev_d2h[p], h.eg.d2h));
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.d2h_bytes += bytes;
+  return true;
+}
+
+// ---- the driver: GPU g's thread of one push
+void x_loop(Run& r, int g) {
+  sg_node& nd = r.nd;
+  r.guarded([&] {
+    HIPCHK(hipSetDevice(nd.dev[g]));
+    XChunk c;
+    for (c.j = 0; c.j < r.nch; ++c.j) {
+      const double t0 = now_ms();
+      c.p = (int)(c.j & 1);
+      if (c.j == 0) x_upload(r, g, 0);
+      if (c.j + 1 < r.nch) x_upload(r, g, c.j + 1);   // (slot (j + 1) & 1 held chunk j - 1, scattered already)
+      int64_t e;
+      x_slice(r, c.j, g, c.a, e);
+      c.n = e - c.a;
+      x_shard(r, g, c);
+      if (!x_send_rows(r, g, c)) return;
+      if (!x_compute(r, g, c)) return;
+      if (r.w.key && !x_assign_ids(r, g, c)) return;
+      x_stage_matches(r, g, c);
+      if (!x_plan_merge(r, g, c)) return;
+      if (!x_send_matches(r, g, c)) return;
+      if (!x_merge_deliver(r, g, c)) return;
+      c.out_before += c.chunk_total;
+      r.publish([&] {
+        r.t_gpu[g] += now_ms() - t0;
+        if (g == 0) r.out_rows = c.out_before;
+      });
+    }
+    HIPCHK(hipStreamSynchronize(nd.h[g]->h.stream));
+    HIPCHK(hipStreamSynchronize(nd.x[g].xs));
+    HIPCHK(hipStreamSynchronize(nd.h[g]->h.eg.d2h));
   });
 }
 
@@ -1791,8 +1945,7 @@ void reserve_all(Run& r) {
   sg_node& nd = r.nd;
   const sg_nfa_desc& d = nd.desc;
   const int64_t C = r.C;
-  int need[SG_MAX_COLS] = {};
-  for (int k = 0; k < d.n_ret; ++k) need[d.ret_col[k]] = 1;
+  const NeedCols nc(d);
   for (int q = 0; q < NODE_RING; ++q) {
     if (nd.G == 1) {
       nd.keyslot[q].ensure((size_t)C * 4);
@@ -1808,9 +1961,9 @@ void reserve_all(Run& r) {
         S.ts32.ensure((size_t)C * 4);
         if (r.b.stream || need_clocks(d)) S.stream.ensure((size_t)C * 4);
         for (int c = 0; c < d.n_cols; ++c) {
-          if (!need[c] || !r.b.cols[c]) continue;
+          if (!nc.col(r.b, c)) continue;
           S.col[c].ensure((size_t)C * sg_col_width(d.col_type[c]));
-          if (r.b.nulls && r.b.nulls[c]) S.nul[c].ensure((size_t)C);
+          if (nc.nul(r.b, c)) S.nul[c].ensure((size_t)C);
         }
       }
     }
@@ -1819,35 +1972,10 @@ void reserve_all(Run& r) {
   for (int s = 0; s < nd.G; ++s) {
     SgHandle& h = nd.h[s]->h;
     HIPCHK(hipSetDevice(nd.dev[s]));
-    sg_batch sb;
-    memset(&sb, 0, sizeof(sb));
-    const void* cols[SG_MAX_COLS] = {};
-    const uint8_t* nuls[SG_MAX_COLS] = {};
-    static const char dummy[1] = {0};
-    sb.ts = (const int64_t*)dummy;
-    sb.key = (const int32_t*)dummy;
-    sb.stream = (r.b.stream || (nd.G > 1 && need_clocks(d))) ? (const int32_t*)dummy : nullptr;
-    bool nul = false;
-    for (int c = 0; c < d.n_cols; ++c) {
-      cols[c] = (need[c] && r.b.cols[c]) ? dummy : nullptr;
-      nuls[c] = (need[c] && r.b.nulls && r.b.nulls[c]) ? (const uint8_t*)dummy : nullptr;
-      nul |= nuls[c] != nullptr;
-    }
-    sb.cols = cols;
-    sb.nulls = nul ? nuls : nullptr;
-    for (int ds = 0; ds < 2; ++ds) nd.dslot[s][ds] = sg_reserve_slot(h, &sb, C, ds);
-    if (nd.dts32_rows < C)
-      for (int ds = 0; ds < 2; ++ds) {
-        if (nd.dts32[s][ds]) HIPCHK(hipFree(nd.dts32[s][ds]));
-        nd.dts32[s][ds] = nullptr;
-        HIPCHK(hipMalloc((void**)&nd.dts32[s][ds], (size_t)C * 4));
-      }
-    if (nd.ddict == 1 && nd.draw_rows < C)
-      for (int ds = 0; ds < 2; ++ds) {
-        if (nd.draw[s][ds]) HIPCHK(hipFree(nd.draw[s][ds]));
-        nd.draw[s][ds] = nullptr;
-        HIPCHK(hipMalloc((void**)&nd.draw[s][ds], (size_t)C * 8));
-      }
+    reserve_slots(nd, s, C, r.b.stream || (nd.G > 1 && need_clocks(d)), false, [&](int c) { return nc.col(r.b, c); },
+                  [&](int c) { return nc.nul(r.b, c); });
+    if (nd.dts32_rows < C) regrow_slots(nd.dts32[s], C);
+    if (nd.ddict == 1 && nd.draw_rows < C) regrow_slots(nd.draw[s], C);
     HIPCHK(hipStreamSynchronize(h.stream));
     sg_egress_init(h);
     // egress slots for one chunk's matches (the closed forms emit at most one match per e1 row, the lane routes rarely
@@ -1906,14 +2034,14 @@ void run_push(sg_node& nd, const sg_node_batch& b, const sg_match_columns* out, 
   double t1 = 0;
   if (xchg) {   // GPU-side shard exchange: one loop per GPU, no host route or merge
     const int G = nd.G;
-    const XSpec sp = xspec_of(nd, b);
+    r.xsp = xspec_of(nd, b);
     r.xst.assign((size_t)(r.nch * G * (G + 1)), 0);
     r.xpc.assign((size_t)(r.nch * G * (G + 1)), 0);
     r.xkbase.assign((size_t)(r.nch * G), 0);
     r.xnf.assign((size_t)(r.nch * G), std::vector<uint64_t>());
-    x_reserve(r, sp);
+    x_reserve(r);
     t1 = now_ms();
-    for (int s = 0; s < G; ++s) th.push_back(tc.run([&r, s, sp] { x_loop(r, s, sp); }));
+    for (int s = 0; s < G; ++s) th.push_back(tc.run([&r, s] { x_loop(r, s); }));
   } else {
   reserve_all(r);
   t1 = now_ms();

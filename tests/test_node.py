@@ -35,12 +35,14 @@ def node_outputs(nfa, sink, n):
             vals[:, k] = c.view(np.int64)
         vnull[:, k] = sink.nulls[k][:n]
     ns = len(dts)
-    return Outputs(sink.trigger[:n].copy(), sink.ts[:n].copy(), sink.key[:n].copy(), sink.group[:n].copy(),
-                   vals[:, :ns], vnull[:, :ns])
+    key = sink.key[:n].copy() if sink.key is not None else np.zeros(n, np.int32)   # (a sink without the key column)
+    return Outputs(sink.trigger[:n].copy(), sink.ts[:n].copy(), key, sink.group[:n].copy(), vals[:, :ns], vnull[:, :ns])
 
 
-def run_node(query, pushes, n_gpus, chunk_rows, raw_of, threads=4, cap=None, pinned=False, key_dict=0):
-    """Push host batches (their .key = synthetic key ids, sent as raw 64-bit symbols) through one node."""
+def run_node(query, pushes, n_gpus, chunk_rows, raw_of, threads=4, cap=None, pinned=False, key_dict=0,
+             fields=("trigger", "ts", "key", "group")):
+    """Push host batches (their .key = synthetic key ids, sent as raw 64-bit symbols) through one node.  The returned
+    stats carry the node's key count as st["keys"]."""
     from siddhi_amd import _native as N
     nfa = __import__("siddhi_amd.lowering", fromlist=["lower"]).lower(context(query))
     node = N.Node(N.build_desc(nfa), n_gpus=n_gpus, devices=[0] * n_gpus, threads=threads, chunk_rows=chunk_rows)
@@ -58,10 +60,15 @@ def run_node(query, pushes, n_gpus, chunk_rows, raw_of, threads=4, cap=None, pin
         nb = N.make_node_batch(b.n, b.base_index, ts.ctypes.data, 0 if st is None else st.ctypes.data,
                                raw.ctypes.data, [c.ctypes.data for c in cols],
                                [0 if x is None else x.ctypes.data for x in nul], keep)
-        sink = N.ColumnSink(nfa, cap or (4 * b.n + 16), pinned=pinned)
-        got = node.push(nb, sink.struct, sink.cap)
+        sink = N.ColumnSink(nfa, cap or (4 * b.n + 16), pinned=pinned, fields=fields)
+        try:
+            got = node.push(nb, sink.struct, sink.cap)
+        except Exception:
+            node.close()
+            raise
         outs.append(node_outputs(nfa, sink, got))
     st = node.stats()
+    st["keys"] = node.keys()
     node.close()
     return Outputs(*[np.concatenate([getattr(o, f) for o in outs]) for f in
                      ("trigger", "ts", "key", "group", "vals", "vnull")]), st
@@ -297,3 +304,79 @@ def test_node_shard_exchange(gpus):
         assert_same(got, want)
         assert st["route_ms"] == 0 and st["merge_ms"] == 0
         assert sum(st["shard_rows"][:gpus]) == n
+
+
+# ---- the exchange's branches that the sizes above never reach: tiny inputs, each a few chunks of a few rows ----------
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("cfg,gpus,chunk", [("C2", 8, 5), ("PP", 3, 7), ("C3c", 3, 7)])
+def test_node_exchange_empty_slices_shards_and_chunks(cfg, gpus, chunk):
+    """400 rows of 7 keys in chunks of 5 rows over 8 GPUs: every chunk has slices of zero rows (no shard count is
+    launched for them), the 7 keys reach only 3 of the 8 shards (the others never resolve or push a row) and 24 of the
+    80 chunks hold no trigger (no shard has matches, no owner merges).  PP and C3c the same way over 3 GPUs."""
+    n = 400
+    b = synth_batch(cfg, 0, n, keys=7, rate=100)
+    want = _want(synth.QUERIES[cfg], b)
+    assert len(want) > 0
+    got, st = run_node(synth.QUERIES[cfg], [b], gpus, chunk, synth.raw_symbols, key_dict=2)
+    assert_same(got, want)
+    assert st["chunks"] == -(-n // chunk)
+    assert sum(st["shard_rows"][:gpus]) == n
+    assert st["route_ms"] == 0 and st["merge_ms"] == 0
+
+
+@pytest.mark.timeout(300)
+def test_node_exchange_fewer_rows_than_gpus():
+    b = synth_batch("C2", 0, 5, keys=2)
+    want = _want(synth.QUERIES["C2"], b)
+    assert len(want) == 2
+    got, st = run_node(synth.QUERIES["C2"], [b], 8, 0, synth.raw_symbols, key_dict=2)
+    assert_same(got, want)
+    assert sum(st["shard_rows"][:8]) == 5
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("chunk", [1000, 100])
+def test_node_exchange_key_table_grows_across_chunks_and_pushes(chunk):
+    """2,578 distinct keys over two shards in two pushes: each GPU's table of node-wide key ids (local id -> first-seen
+    id) is appended to chunk after chunk and push after push.  It is allocated for 1.5 x the first chunk's keys + 1024:
+    with 1000-row chunks that holds a shard's ~1,290 keys to the end; with 100-row chunks (~50 keys per shard in the
+    first) the table is outgrown and copied into a larger one."""
+    cfg = "C2"
+    b = synth_batch(cfg, 0, 6000, keys=3000, rate=100)
+    want = _want(synth.QUERIES[cfg], b)
+    assert len(want) > 0
+    got, st = run_node(synth.QUERIES[cfg], _split(b, [0, 2500, 6000]), 2, chunk, synth.raw_symbols, key_dict=2)
+    assert_same(got, want)   # (keys: the oracle's first-seen ids)
+    assert st["keys"] == len(np.unique(b.key))
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("gpus", [2, 4])
+def test_node_exchange_without_key_column(gpus):
+    """A sink without the key column: the exchange skips the node-wide key ids altogether."""
+    cfg = "C2"
+    b = synth_batch(cfg, 0, 400, keys=7, rate=100)
+    want = _want(synth.QUERIES[cfg], b)
+    assert len(want) > 0
+    got, _ = run_node(synth.QUERIES[cfg], [b], gpus, 60, synth.raw_symbols, key_dict=2,
+                      fields=("trigger", "ts", "group"))
+    assert len(got) == len(want)
+    for f in ("trigger", "ts", "group", "vnull"):
+        assert np.array_equal(getattr(got, f), getattr(want, f)), f
+    assert np.array_equal(np.where(got.vnull.astype(bool), 0, got.vals), np.where(want.vnull.astype(bool), 0, want.vals))
+
+
+@pytest.mark.timeout(300)
+def test_node_exchange_capacity_error():
+    """More matches than the output capacity, through the exchange: every GPU's loop ends (none is left waiting for a
+    step the others gave up) and the push reports SG_ECAPACITY; a fresh node with room delivers the oracle's rows."""
+    from siddhi_amd._native import SgError
+    cfg = "C2"
+    b = synth_batch(cfg, 0, 400, keys=7, rate=100)
+    want = _want(synth.QUERIES[cfg], b)
+    assert len(want) > 80
+    with pytest.raises(SgError) as ei:
+        run_node(synth.QUERIES[cfg], [b], 2, 100, synth.raw_symbols, key_dict=2, cap=80)
+    assert ei.value.code == -3
+    got, _ = run_node(synth.QUERIES[cfg], [b], 2, 100, synth.raw_symbols, key_dict=2)
+    assert_same(got, want)
