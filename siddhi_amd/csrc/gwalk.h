@@ -48,16 +48,16 @@ struct GwArgs {
   int64_t n, nc;              // batch rows; carried rows (virtual rows [0, nc))
   int64_t within;
   int64_t t0;                 // narrow records' time origin (the push's first virtual row)
-  uint32_t K, ns1;            // keys; pass-1 segments per group (o1 stride)
+  uint32_t K, nc1;            // keys; columns per group of the group table (o1 stride)
   int32_t stack_mode;
   int32_t cap;                // LDS ring entries per lane (power of two)
   int32_t chunk;              // rows per LDS chunk (multiple of 256)
   int32_t carry_out;
   int32_t pzero;              // payload bits zero-extended (FLOAT) rather than sign-extended
-  const uint32_t* o1;         // group g's rows: [o1[g * ns1], o1[(g + 1) * ns1])
+  const uint32_t* o1;         // group g's rows: [o1[g * nc1], o1[(g + 1) * nc1])
   const PtU4* grec;           // pass 1b's records, grouped by group, arrival order within a group
   const uint8_t* glk;         // in-group key of each record
-  const uint32_t* kbase;      // per key: its first row in the group domain (exclusive scan of per-key rows)
+  const uint32_t* kbase;      // per key: its first row in the group domain (k_gw_count); kbase[K]: the row count
   uint64_t* trig;             // per batch row: gw_trig_word(match-area unit of its header, matches, epoch)
   uint32_t epoch;             // this push's tag (1..255): a word tagged otherwise is no trigger
   uint64_t* area;             // match area, 8-byte units: 3 per row of the key
@@ -86,19 +86,44 @@ __device__ __forceinline__ uint32_t gw_trig_matches(uint64_t w, uint32_t epoch) 
   return (uint32_t)(w >> 56) == epoch ? (uint32_t)(w >> 32) & GW_MATCH_MAX : 0u;
 }
 
-// per-key rows of every group (LDS counters over the group's in-group keys)
-static __global__ void __launch_bounds__(256) k_gw_count(const uint32_t* __restrict__ o1, uint32_t ns1, uint32_t K,
-                                                         const uint8_t* __restrict__ glk, uint32_t* __restrict__ kcnt) {
+// per-key rows of every group (LDS counters over the group's in-group keys, read 16 bytes per lane between a scalar
+// head and tail) -> each key's first row in the group domain: the group's keys lie one after the other from the
+// group's own first row, so kbase[k] = o1[g * nc1] + the rows of the group's keys before k; kbase[K] = the row count
+static __global__ void __launch_bounds__(256) k_gw_count(const uint32_t* __restrict__ o1, uint32_t nc1, uint32_t K,
+                                                         const uint8_t* __restrict__ glk, uint32_t* __restrict__ kbase) {
   __shared__ uint32_t c[4][256];
+  __shared__ uint32_t wsum[4];
   const uint32_t g = blockIdx.x, t = threadIdx.x, w = t >> 6;
 #pragma unroll
   for (int q = 0; q < 4; ++q) c[q][t] = 0;
   __syncthreads();
-  const uint32_t lo = o1[(size_t)g * ns1], hi = o1[(size_t)(g + 1) * ns1];
-  for (uint32_t p = lo + t; p < hi; p += 256) atomicAdd(&c[w][glk[p]], 1u);
+  const uint32_t lo = o1[(size_t)g * nc1], hi = o1[(size_t)(g + 1) * nc1];
+  const uint32_t mis = (uint32_t)(16u - ((uintptr_t)(glk + lo) & 15u)) & 15u;
+  const uint32_t a0 = min(hi, lo + mis);   // the first 16-byte aligned position (or the end)
+  const uint32_t nv = (hi - a0) >> 4;      // whole 16-byte words from there
+  const uint32_t a1 = a0 + (nv << 4);
+  if (t < a0 - lo) atomicAdd(&c[w][glk[lo + t]], 1u);
+  if (t < hi - a1) atomicAdd(&c[w][glk[a1 + t]], 1u);
+  const PtU4* v = (const PtU4*)(glk + a0);
+  auto count = [&](const PtU4& x) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int b = 0; b < 32; b += 8) atomicAdd(&c[w][(x[q] >> b) & 255u], 1u);
+  };
+  for (uint32_t i = t; i < nv; i += 512) {   // two words per lane in flight
+    const PtU4 x0 = v[i];
+    const bool two = i + 256 < nv;
+    const PtU4 x1 = v[two ? i + 256 : i];
+    count(x0);
+    if (two) count(x1);
+  }
   __syncthreads();
+  const uint32_t n = c[0][t] + c[1][t] + c[2][t] + c[3][t];
+  const uint32_t first = lo + block_excl_scan256(n, wsum);
   const uint32_t k = (g << 8) + t;
-  if (k < K) kcnt[k] = c[0][t] + c[1][t] + c[2][t] + c[3][t];
+  if (k < K) kbase[k] = first;
+  if (k + 1 == K) kbase[K] = first + n;
 }
 
 template <int PT>
@@ -256,7 +281,7 @@ __global__ void __launch_bounds__(256, 1) k_gwalk(GwArgs a) {
   const uint32_t g = xcd_block(blockIdx.x, gridDim.x);
   const uint32_t k = (g << 8) + t;
   const bool active = k < a.K;
-  const uint32_t lo = a.o1[(size_t)g * a.ns1], hi = a.o1[(size_t)(g + 1) * a.ns1];
+  const uint32_t lo = a.o1[(size_t)g * a.nc1], hi = a.o1[(size_t)(g + 1) * a.nc1];
   GwLane<T, OP, STACK, GwLdsRing<T>> W;
   W.R.v = (T*)(lds_raw + sizeof(GwLds<PT>));            // ring planes [cap][256]: value, time, payload
   W.R.t = (int32_t*)(W.R.v + (size_t)cap * 256);
@@ -384,7 +409,7 @@ __global__ void __launch_bounds__(256) k_gw_redo(GwArgs a, uint32_t* __restrict_
   __shared__ int32_t red_t[GW_REDO_LDS], red_p[GW_REDO_LDS];
   const uint32_t k = a.ovf_keys[blockIdx.x];
   const uint32_t g = k >> 8, d = k & 255u, t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const uint32_t lo = a.o1[(size_t)g * a.ns1], hi = a.o1[(size_t)(g + 1) * a.ns1];
+  const uint32_t lo = a.o1[(size_t)g * a.nc1], hi = a.o1[(size_t)(g + 1) * a.nc1];
   const uint32_t kb = a.kbase[k], ke = a.kbase[k + 1];
   if (t == 0) base_s = 0;
   __syncthreads();
@@ -681,13 +706,10 @@ static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t n
   const int64_t nt = nc + n;
   const uint32_t ng = (kb + 255) >> 8;
   // per-key rows -> each key's first row in the group domain (its match-area region starts at 3x that)
-  uint32_t* kcnt = (uint32_t*)h->ws.get("gw_kcnt", sizeof(uint32_t) * ((size_t)kb + 1), st);
   uint32_t* kbase = (uint32_t*)h->ws.get("gw_kbase", sizeof(uint32_t) * ((size_t)kb + 1), st);
   h->kbeg("gw_count");
-  HIPCHK(hipMemsetAsync(kcnt, 0, sizeof(uint32_t) * ((size_t)kb + 1), st));
-  hipLaunchKernelGGL(k_gw_count, dim3(ng), dim3(256), 0, st, o1, pp.ns1, kb, glk, kcnt);
+  hipLaunchKernelGGL(k_gw_count, dim3(ng), dim3(256), 0, st, o1, pp.nc1, kb, glk, kbase);
   HIPCHK(hipGetLastError());
-  sg_exclusive_scan(h->ws, st, "gw_kscan_tmp", kcnt, kbase, (uint32_t)0, (size_t)kb + 1, rocprim::plus<uint32_t>());
   h->kend();
   uint32_t pkf = 0;
   int64_t t0 = 0;   // narrow records' time origin: the push's first virtual row
@@ -706,7 +728,7 @@ static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t n
   ga.within = d.within;
   ga.t0 = t0;
   ga.K = kb;
-  ga.ns1 = pp.ns1;
+  ga.nc1 = pp.nc1;
   ga.stack_mode = stack_mode;
   ga.cap = gp.cap;
   ga.chunk = 4096;

@@ -41,6 +41,8 @@ struct PartPlan {
   uint32_t nb1, nb2;          // bits that tell the digits apart (ballots per 64-row step)
   uint32_t seg1, ns1;         // rows per pass-1 segment (multiple of PT1_ROWS); pass-1 segments
   uint32_t ts2, nj;           // pass-1 segments per pass-2 segment; pass-2 segments per group
+  uint32_t w1, nc1;           // group table o1: pass-1 segments per column; columns per group (its stride).  One
+                              // column per segment (w1 = 1, nc1 = ns1) up to 65,536 keys, P1_COL_SEGS beyond (part1_wide)
 };
 
 template <class R, int PT, class TG = uint16_t>
@@ -222,11 +224,13 @@ __global__ void __launch_bounds__(256) k_part1(PackFn<T, N> pk, KeyOf kf, PartPl
   if (bad) atomicOr(flags, bad);
 }
 
-// pass-2 segment (g, jj): group g's rows that came from pass-1 segments [jj*ts2, (jj+1)*ts2)
+// pass-2 segment (g, jj): group g's rows that came from pass-1 segments [jj*ts2, (jj+1)*ts2) -- whole columns of o1
+// (ts2 is a multiple of w1)
 __device__ __forceinline__ void part2_range(const PartPlan& pp, const uint32_t* o1, uint32_t g, uint32_t jj,
                                             uint32_t& lo, uint32_t& hi) {
-  lo = o1[(size_t)g * pp.ns1 + jj * pp.ts2];
-  hi = o1[(size_t)g * pp.ns1 + min(pp.ns1, (jj + 1) * pp.ts2)];
+  const uint32_t cs = pp.ts2 / pp.w1;
+  lo = o1[(size_t)g * pp.nc1 + jj * cs];
+  hi = o1[(size_t)g * pp.nc1 + min(pp.nc1, (jj + 1) * cs)];
 }
 
 static __global__ void __launch_bounds__(256) k_part2_hist(PartPlan pp, const uint32_t* __restrict__ o1,
@@ -352,55 +356,77 @@ static PartPlan part_plan(uint32_t K, int64_t nt) {
   // pass-2 segments of ~8192 rows of one group
   p.ts2 = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(p.ns1, (int64_t)8192 * p.ng / p.seg1));
   p.nj = (p.ns1 + p.ts2 - 1) / p.ts2;
+  p.w1 = 1;
+  p.nc1 = p.ns1;
   return p;
 }
 
 // ---- more than 256 key groups (C5's 1M keys): the group domain in two passes.  Pass 1a groups rows by supergroup
 // (k_part1 with 32-bit staged keys and 16-bit in-supergroup keys); pass 1b splits each supergroup into its groups,
-// arrival order kept, straight into the group-domain positions of the per-(group, segment) histogram (o1).
+// arrival order kept, straight into the group-domain positions of the group table (o1).  Pass 1a needs offsets per
+// pass-1 segment (oa); every reader of the group table reads it at a multiple of tsb or ts2 segments or at a group's
+// first row, so that table has one column per P1_COL_SEGS segments, and tsb and ts2 are multiples of that.
+static const uint32_t P1_COL_SEGS = 8;
 
-// per part1 segment j: rows of each group g -> h[g * ns1 + j] (up to 4096 groups, LDS counters), and of each
-// supergroup (2^lbs consecutive groups) -> ha[sg * ns1 + j] from the same counters (one pass over the keys)
+// per column jj of w1 part1 segments: rows of each group g -> h[g * nc1 + jj] (up to 4096 groups, LDS counters that
+// run on over the column's segments), and per segment j the rows of each supergroup (2^lbs consecutive groups; at most
+// 64 of them) -> ha[sg * ns1 + j] from the same counters (one pass over the keys)
 static __global__ void __launch_bounds__(256) k_hist_wide(KeyOf kf, uint32_t K, uint32_t lb, uint32_t ng, uint32_t seg1,
-                                                          uint32_t ns1, int64_t nt, uint32_t* __restrict__ h,
-                                                          uint32_t lbs, uint32_t nsg, uint32_t* __restrict__ ha,
-                                                          uint32_t* __restrict__ flags) {
+                                                          uint32_t ns1, uint32_t w1, uint32_t nc1, int64_t nt,
+                                                          uint32_t* __restrict__ h, uint32_t lbs, uint32_t nsg,
+                                                          uint32_t* __restrict__ ha, uint32_t* __restrict__ flags) {
   __shared__ uint32_t cnt[4096];
-  const uint32_t j = blockIdx.x, t = threadIdx.x;
+  __shared__ uint32_t sgc[64];   // each supergroup's rows in the column's segments so far
+  const uint32_t jj = blockIdx.x, t = threadIdx.x, w = t >> 6, lane = t & 63;
   for (uint32_t g = t; g < ng; g += 256) cnt[g] = 0;
+  if (t < 64) sgc[t] = 0;
   __syncthreads();
-  const int64_t r0 = (int64_t)j * seg1, r1 = min(nt, r0 + seg1);
   uint32_t bad = 0;
-  for (int64_t rb = r0; rb < r1; rb += 256 * 8) {   // eight rows per thread in flight
-    uint32_t k[8];
+  const uint32_t j1 = min(ns1, (jj + 1) * w1), nd = 1u << lbs;
+  for (uint32_t j = jj * w1; j < j1; ++j) {
+    const int64_t r0 = (int64_t)j * seg1, r1 = min(nt, r0 + seg1);
+    for (int64_t rb = r0; rb < r1; rb += 256 * 8) {   // eight rows per thread in flight
+      uint32_t k[8];
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const int64_t r = rb + s * 256 + t;
-      k[s] = r < r1 ? kf((uint32_t)r) : 0xffffffffu;
-    }
+      for (int s = 0; s < 8; ++s) {
+        const int64_t r = rb + s * 256 + t;
+        k[s] = r < r1 ? kf((uint32_t)r) : 0xffffffffu;
+      }
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      if (k[s] < K) atomicAdd(&cnt[k[s] >> lb], 1u);
-      else if (k[s] != 0xffffffffu) bad |= PK_KEY_RANGE;
+      for (int s = 0; s < 8; ++s) {
+        if (k[s] < K) atomicAdd(&cnt[k[s] >> lb], 1u);
+        else if (k[s] != 0xffffffffu) bad |= PK_KEY_RANGE;
+      }
     }
+    __syncthreads();
+    // a wave per supergroup: its groups' counters summed across the lanes
+    for (uint32_t sg = w; sg < nsg; sg += 4) {
+      uint32_t c = 0;
+      for (uint32_t i = lane; i < nd; i += 64) {
+        const uint32_t g = (sg << lbs) + i;
+        c += g < ng ? cnt[g] : 0u;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
+      if (lane == 0) {
+        ha[(size_t)sg * ns1 + j] = c - sgc[sg];
+        sgc[sg] = c;
+      }
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  for (uint32_t g = t; g < ng; g += 256) h[(size_t)g * ns1 + j] = cnt[g];
-  for (uint32_t sg = t; sg < nsg; sg += 256) {
-    uint32_t c = 0;
-    for (uint32_t g = sg << lbs; g < ((sg + 1) << lbs) && g < ng; ++g) c += cnt[g];
-    ha[(size_t)sg * ns1 + j] = c;
-  }
+  for (uint32_t g = t; g < ng; g += 256) h[(size_t)g * nc1 + jj] = cnt[g];
   if (bad) atomicOr(flags, bad);
 }
 
 struct Part1bArgs {
   uint32_t lb;          // in-group key bits
   uint32_t lbs;         // group bits inside a supergroup
-  uint32_t ns1, tsb;    // part1 segments; per pass-1b segment
+  uint32_t ns1, tsb;    // part1 segments; per pass-1b segment (a multiple of w1)
   uint32_t nsb;         // pass-1b segments per supergroup
+  uint32_t ng, w1, nc1; // groups; part1 segments per column of o1; its columns per group
   const uint32_t* oa;   // pass-1a offsets [sg * ns1 + j]
-  const uint32_t* o1;   // group-domain offsets [g * ns1 + j]
+  const uint32_t* o1;   // group-domain offsets [g * nc1 + j / w1]
 };
 
 template <int PT>
@@ -423,7 +449,7 @@ __global__ void __launch_bounds__(256) k_part1b(Part1bArgs B, const PtU4* __rest
   const uint32_t jf = min(B.ns1, jj * B.tsb), jl = min(B.ns1, jf + B.tsb);
   const uint32_t lo = B.oa[(size_t)sg * B.ns1 + jf], hi = B.oa[(size_t)sg * B.ns1 + jl];
   const uint32_t nd = 1u << B.lbs, lmask = (1u << B.lb) - 1u;
-  if (t < nd) L.run[t] = B.o1[(size_t)((sg << B.lbs) | t) * B.ns1 + jf];
+  if (t < nd && ((sg << B.lbs) | t) < B.ng) L.run[t] = B.o1[(size_t)((sg << B.lbs) | t) * B.nc1 + jf / B.w1];
   const int ROWS = 256 * PT;
   auto load = [&](uint32_t base, PtU4* rc, uint32_t* tg) {
     const uint32_t rows = min((uint32_t)ROWS, hi - base);
@@ -493,7 +519,8 @@ __global__ void __launch_bounds__(256) k_part1b(Part1bArgs B, const PtU4* __rest
 // Pass 1 of the key partition beyond 256 key groups (up to 4096 groups of 2^pp.lb keys, e.g. C5's 1M keys): rows ->
 // narrow walker records grouped by key group, arrival order kept inside a group, in two LDS counting passes --
 // supergroups of 2^lbs groups (<= 64 of them, k_part1 with 32-bit staged keys), then the groups inside each
-// supergroup (k_part1b) straight into the group positions o1[g * ns1 + j] of the per-(group, segment) histogram.
+// supergroup (k_part1b) straight into the group positions of the group table: o1[g * nc1 + c] is the first position of
+// group g's rows from part1 segment c * w1 on (after every row of the groups before it), o1[ng * nc1] the row count.
 // Output: grec, glk (in-group key), o1.
 template <class T>
 static void part1_wide(SgHandle* h, const PackFn<T, true>& pk, KeyOf kf, uint32_t kb, int64_t nt, const PartPlan& pp,
@@ -501,7 +528,7 @@ static void part1_wide(SgHandle* h, const PackFn<T, true>& pk, KeyOf kf, uint32_
   typedef WRec<T, true> R;
   hipStream_t st = h->stream;
   const uint32_t lb = pp.lb, ng = pp.ng;
-  const size_t n1 = (size_t)pp.ng * pp.ns1 + 1;
+  const size_t n1 = (size_t)pp.ng * pp.nc1 + 1;
   {
     // two passes: supergroups of 2^lbs groups (<= 64 of them), then groups inside each supergroup.  (C5, 4096 groups,
     // per 500M-row push: 256 supergroups part_group 7.7 + part_split 3.8 ms; 64 supergroups 6.0 + 4.2 ms -- pass 1's
@@ -522,8 +549,8 @@ static void part1_wide(SgHandle* h, const PackFn<T, true>& pk, KeyOf kf, uint32_
     h->kbeg("part_hist");
     HIPCHK(hipMemsetAsync(hA + nA - 1, 0, sizeof(uint32_t), st));
     HIPCHK(hipMemsetAsync(h1 + n1 - 1, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_hist_wide, dim3(pp.ns1), dim3(256), 0, st, kf, kb, lb, ng, pp.seg1, pp.ns1, nt, h1, lbs, pa2.ng, hA,
-                       pk_flags);
+    hipLaunchKernelGGL(k_hist_wide, dim3(pp.nc1), dim3(256), 0, st, kf, kb, lb, ng, pp.seg1, pp.ns1, pp.w1, pp.nc1, nt, h1,
+                       lbs, pa2.ng, hA, pk_flags);
     HIPCHK(hipGetLastError());
     sg_exclusive_scan(h->ws, st, "part_scan_tmpA", (const uint32_t*)hA, oA, (uint32_t)0, nA, rocprim::plus<uint32_t>());
     sg_exclusive_scan(h->ws, st, "part_scan_tmp", (const uint32_t*)h1, o1, (uint32_t)0, n1, rocprim::plus<uint32_t>());
@@ -551,9 +578,16 @@ static void part1_wide(SgHandle* h, const PackFn<T, true>& pk, KeyOf kf, uint32_
     B.lbs = lbs;
     B.ns1 = pp.ns1;
     const int64_t per_sg = std::max<int64_t>(1, nt / pa2.ng);
-    B.nsb = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(pp.ns1, per_sg / 32768));
+    // (rows of a supergroup per pass-1b segment: SG_DEBUG_P1B_ROWS test hook, several segments in a small push)
+    const char* be = getenv("SG_DEBUG_P1B_ROWS");
+    const int64_t rows_b = be ? std::max(atoi(be), 1) : 32768;
+    B.nsb = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(pp.ns1, per_sg / rows_b));
     B.tsb = (pp.ns1 + B.nsb - 1) / B.nsb;
+    B.tsb = (B.tsb + pp.w1 - 1) / pp.w1 * pp.w1;   // whole columns of o1
     B.nsb = (pp.ns1 + B.tsb - 1) / B.tsb;
+    B.ng = ng;
+    B.w1 = pp.w1;
+    B.nc1 = pp.nc1;
     B.oa = oA;
     B.o1 = o1;
     const size_t ldsB = sizeof(Part1bLds<16>);
@@ -633,10 +667,13 @@ static PartLdsBufs<T, N> part_lds_bufs(const PushCtx& c) {
     pp.nb1 = 0;
     while ((1u << pp.nb1) < pp.ng) ++pp.nb1;
     pp.nb2 = 8;
+    pp.w1 = P1_COL_SEGS;
+    pp.nc1 = (pp.ns1 + pp.w1 - 1) / pp.w1;
     pp.ts2 = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(pp.ns1, (int64_t)8192 * pp.ng / pp.seg1));
+    pp.ts2 = (pp.ts2 + pp.w1 - 1) / pp.w1 * pp.w1;   // whole columns of o1
     pp.nj = (pp.ns1 + pp.ts2 - 1) / pp.ts2;
   }
-  b.n1 = (size_t)pp.ng * pp.ns1 + 1;
+  b.n1 = (size_t)pp.ng * pp.nc1 + 1;
   b.h1 = (uint32_t*)h->ws.get("part_h1", sizeof(uint32_t) * b.n1, st);
   b.o1 = (uint32_t*)h->ws.get("part_o1", sizeof(uint32_t) * b.n1, st);
   b.srec = (R*)h->ws.get("srec", sizeof(R) * c.nt, st);
