@@ -389,6 +389,22 @@ int sg_node_reset(sg_node* nd);   /* new stream: forget keys and per-key state *
  * router (sg_router), 2 one dictionary per GPU in HBM (raw keys are uploaded; with several GPUs rows go to shard
  * mix64(raw) mod n_gpus).  Only before the first push of a stream. */
 int sg_node_set_key_dict(sg_node* nd, int mode);
+/* Range partitions inside the node: rows of a range-partitioned stream are routed on the GPUs after upload
+ * (one copy per holding range, written order), before sharding.  label_raw[l] is the raw 64-bit partition-key
+ * value of label code l, in the same space as sg_node_batch.raw_key (for string keys: the caller's dictionary id
+ * of the label string), so a value key and a label with the same string stay one instance.  raw_key entries of
+ * rows of range streams are ignored.  Only before the first push of a stream; survives sg_node_reset.
+ * With ranges set, out->trigger is still the event index (base_index + row) of the row whose arrival produced the
+ * match, the matches of one event come in the written order of the ranges that hold it, out->key is the node-wide
+ * first-seen id in creation order over (event, range position), and sg_node_stats.shard_rows counts copies.  A row
+ * that holds no range is dropped.  chunk_rows 0 is divided by the most ranges one stream has.
+ * SG_EINVAL: a bad descriptor or ABI version, n_cols / col_type / col_stream that are not the query's, a call after
+ * the first push or after sg_node_set_key_dict(nd, 1) (range routing uses the device dictionary); sg_node_push then
+ * returns SG_EINVAL for a base_index + n at or above 2^(63 - ceil(log2(most ranges of one stream))).
+ * SG_EUNSUPPORTED: a program deeper than the VM stack, an unpartitioned query, a query with playback timers (those
+ * keep the host route: expand on the host or with sg_range_route, then push the copies). */
+int sg_node_set_ranges(sg_node* nd, const sg_range_desc* d, const int64_t* label_raw);
+int sg_node_range_stats_get(const sg_node* nd, sg_range_stats* st);   /* rows in / copies out since open or reset */
 int sg_node_stats_get(const sg_node* nd, sg_node_stats* st);
 int sg_node_keys(const sg_node* nd, int64_t* n_keys);
 int sg_node_close(sg_node* nd);

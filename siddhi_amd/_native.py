@@ -23,7 +23,8 @@ SYMBOLS = ["sg_open", "sg_push", "sg_advance_time", "sg_pending", "sg_poll", "sg
            "sg_router_open", "sg_router_route", "sg_router_keys", "sg_router_close", "sg_router_dense_ids",
            "sg_merge_order", "sg_node_open", "sg_node_push", "sg_node_reset", "sg_node_stats_get", "sg_node_keys",
            "sg_node_close", "sg_node_last_error", "sg_node_set_key_dict", "sg_range_open", "sg_range_route",
-           "sg_range_stats_get", "sg_range_close", "sg_range_last_error"]
+           "sg_range_stats_get", "sg_range_close", "sg_range_last_error", "sg_node_set_ranges",
+           "sg_node_range_stats_get"]
 
 I32, I64, U64 = ct.c_int32, ct.c_int64, ct.c_uint64
 
@@ -200,6 +201,8 @@ def load_library(path: str = LIB_PATH):
         lib.sg_node_keys.argtypes = [P, ct.POINTER(I64)]
         lib.sg_node_close.argtypes = [P]
         lib.sg_node_set_key_dict.argtypes = [P, ct.c_int]
+        lib.sg_node_set_ranges.argtypes = [P, P, P]
+        lib.sg_node_range_stats_get.argtypes = [P, P]
         lib.sg_node_last_error.argtypes = [P]
         lib.sg_node_last_error.restype = ct.c_char_p
         lib.sg_range_open.argtypes = [ct.c_int, P, ct.POINTER(P)]
@@ -605,6 +608,20 @@ class Node:
     def set_key_dict(self, mode: int):
         """0 auto, 1 host router, 2 device dictionary (before the first push of a stream)."""
         self.check(self.lib.sg_node_set_key_dict(self.n, int(mode)))
+
+    def set_ranges(self, desc: sg_range_desc, label_raw):
+        """sg_node_set_ranges: rows of range-partitioned streams are routed on the GPUs inside the node.  desc from
+        build_range_desc(lowering.lower_ranges(ctx)); label_raw[l]: the raw 64-bit key value of label code l, in the
+        space of sg_node_batch.raw_key.  Before the first push of a stream."""
+        raw = np.ascontiguousarray(label_raw, np.int64)
+        assert len(raw) >= desc.n_labels
+        self.check(self.lib.sg_node_set_ranges(self.n, ct.byref(desc), raw.ctypes.data))
+
+    def range_stats(self) -> sg_range_stats:
+        """rows in / copies out of the node's range routing since open or reset"""
+        st = sg_range_stats()
+        self.check(self.lib.sg_node_range_stats_get(self.n, ct.byref(st)))
+        return st
 
     def close(self):
         if self.n:

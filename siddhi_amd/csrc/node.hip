@@ -9,9 +9,11 @@
 // exchange (x_loop below).  Each GPU uploads a contiguous slice of the caller's rows, shards them on the device,
 // exchanges rows with the other GPUs (peer copies), runs its shard, sends each match to the GPU that owns its trigger's
 // slice, and that GPU merges by trigger and copies straight into the caller's columns -- the host does no per-row or
-// per-match work.
+// per-match work.  With range partitions (sg_node_set_ranges) the same exchange runs at any G, one included: between
+// upload and sharding the GPUs give every row of a range stream one copy per range it holds (RangePartitionExecutors in
+// written order, C/partition/PartitionStreamReceiver.java:94-100,270-275), each bound for the shard of its label.
 //
-// One GPU, or queries whose playback timers need every row's clock on every shard (host key dictionary):
+// One GPU without ranges, or queries whose playback timers need every row's clock on every shard (host key dictionary):
 //   route    host thread pool: raw partition-key values -> first-seen dense ids -> shard (GPU) + per-shard id
 //            (router.h); with G > 1 every chunk's rows are scattered, in arrival order, into per-shard pinned
 //            staging (clock rows fan out to every shard), keeping each row's global event index on the host
@@ -44,6 +46,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "keydict.h"
+#include "ranges.h"
 #include "router.h"
 #include "sg_engine.h"
 
@@ -360,6 +363,147 @@ __global__ void __launch_bounds__(256) k_xscatter(XCols in, XCols out, XSpec sp,
   }
 }
 
+// ---- range partitions (sg_node_set_ranges): the same two passes with one copy per holding range -------------------
+// A row of a range stream goes, once per range it holds (k_rr_hold's mask, ranges.h), to the shard of that range's
+// label; every other row goes to its raw key's shard as above.  A copy's index is (event index << shift) | the range's
+// position among its stream's ranges: unique, and increasing in (event, range position) on every shard.
+struct XrTab {   // HBM, built on the host when the ranges are set
+  uint32_t ranged_streams;                         // bit s: stream s has ranges
+  uint32_t shard_mask[SG_MAX_STREAMS][MAX_GPUS];   // [stream][shard]: the stream's ranges whose label lives there
+  int64_t range_raw[SG_MAX_RANGES];                // raw key of the range's label
+  uint32_t range_pos[SG_MAX_RANGES];               // position among its stream's ranges
+};
+static_assert(SG_MAX_STREAMS * MAX_GPUS == 256, "k_xrcount stages the shard table with one word per thread");
+const uint32_t XR_PASS = 0x20;   // slot entry (row in step | what << 8): what < 32 a range, XR_PASS the row itself
+
+__global__ void __launch_bounds__(256) k_xrcount(const int64_t* __restrict__ raw, const int32_t* __restrict__ stream,
+                                                 const uint32_t* __restrict__ masks, const XrTab* __restrict__ tab,
+                                                 int64_t n, uint32_t G, uint32_t* __restrict__ bcnt, uint32_t nblk) {
+  __shared__ uint32_t c[MAX_GPUS];
+  __shared__ uint32_t sm[SG_MAX_STREAMS * MAX_GPUS];   // the shard table (256 words: one per thread)
+  const uint32_t t = threadIdx.x, b = blockIdx.x;
+  if (t < MAX_GPUS) c[t] = 0;
+  sm[t] = tab->shard_mask[t / MAX_GPUS][t % MAX_GPUS];
+  __syncthreads();
+  const int64_t base = (int64_t)b * XB_ROWS;
+  const uint32_t rs = tab->ranged_streams;
+  // the thread's 8 rows in registers: hold mask and stream of a ranged row, the shard of any other (0xff: no copy)
+  uint32_t m[XB_ROWS / 256], sti[XB_ROWS / 256], own[XB_ROWS / 256];
+#pragma unroll
+  for (int k = 0; k < XB_ROWS / 256; ++k) {
+    const int64_t i = base + k * 256 + t;
+    m[k] = 0;
+    sti[k] = 0;
+    own[k] = 0xffu;
+    if (i >= n) continue;
+    const int st = stream ? stream[i] : 0;
+    if (rr_ranged(rs, st)) {
+      m[k] = masks[i];
+      sti[k] = (uint32_t)st;
+    } else if (st >= 0) {   // (st < 0: a clock row)
+      own[k] = (uint32_t)(xmix64((uint64_t)raw[i]) % G);
+    }
+  }
+  // per shard: the thread's copies, summed over the wave, one LDS atomic per wave
+  for (uint32_t s = 0; s < G; ++s) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < XB_ROWS / 256; ++k) v += (uint32_t)__popc(m[k] & sm[sti[k] * MAX_GPUS + s]) + (own[k] == s ? 1u : 0u);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((t & 63) == 0 && v) atomicAdd(&c[s], v);
+  }
+  __syncthreads();
+  if (t < G) bcnt[(size_t)t * nblk + b] = c[t];
+}
+
+// Stable scatter of the copies: 256 source rows per step and, per shard, the step's copies listed in LDS ((row, range
+// position) order) 256 slots at a time and stored destination-major -- consecutive threads write consecutive rows of
+// the send buffer, however many copies one source row has.  A row's count per shard is the function k_xrcount used, so
+// the stores stay inside the block's counted share; `cap` (rows allocated) guards them all the same.
+__global__ void __launch_bounds__(256) k_xrscatter(XCols in, XCols out, XSpec sp, int64_t n, uint64_t gbase,
+                                                   uint32_t shift, int64_t cap, const uint32_t* __restrict__ masks,
+                                                   const XrTab* __restrict__ tab, const uint32_t* __restrict__ boff,
+                                                   uint32_t nblk, uint32_t G) {
+  __shared__ uint32_t s_cur[MAX_GPUS];
+  __shared__ uint32_t s_wtot[4];
+  __shared__ uint32_t s_slot[256];
+  const uint32_t t = threadIdx.x, b = blockIdx.x, w = t >> 6, lane = t & 63;
+  if (t < G) s_cur[t] = boff[(size_t)t * nblk + b];
+  __syncthreads();
+  const int64_t base = (int64_t)b * XB_ROWS;
+  const uint32_t rs = tab->ranged_streams;
+  for (int k = 0; k < XB_ROWS / 256; ++k) {   // 256 rows per step, in arrival order
+    const int64_t row0 = base + k * 256;
+    if (row0 >= n) break;   // (block-uniform)
+    const int64_t i = row0 + t;
+    int st = -1;
+    uint32_t mask = 0, own = 0xffu;
+    bool ranged = false;
+    if (i < n) {
+      st = in.stream ? in.stream[i] : 0;
+      ranged = rr_ranged(rs, st);
+      if (ranged) mask = masks[i];
+      else if (st >= 0) own = (uint32_t)(xmix64((uint64_t)in.raw[i]) % G);
+    }
+    const int sti = ranged ? st : 0;
+    for (uint32_t s = 0; s < G; ++s) {
+      const uint32_t ms = mask & tab->shard_mask[sti][s];   // (mask is 0 unless ranged)
+      const uint32_t cnt = ranged ? (uint32_t)__popc(ms) : (own == s ? 1u : 0u);
+      uint32_t incl = cnt;   // inclusive prefix over the wave
+#pragma unroll
+      for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+      }
+      if (lane == 63) s_wtot[w] = incl;
+      const uint32_t cur = s_cur[s];
+      __syncthreads();
+      uint32_t pre = incl - cnt, total = 0;
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) {
+        if (q < w) pre += s_wtot[q];
+        total += s_wtot[q];
+      }
+      // this thread's slots are [pre, pre + cnt); `q` walks them as the 256-slot windows pass, `rm` holds the ranges left
+      uint32_t q = pre, rm = ms;
+      const uint32_t end = pre + cnt;
+      for (uint32_t lo = 0; lo < total; lo += 256) {
+        const uint32_t hi = lo + 256;
+        while (q < end && q < hi) {
+          uint32_t what = XR_PASS;
+          if (ranged) {
+            what = (uint32_t)__builtin_ctz(rm);
+            rm &= rm - 1;
+          }
+          s_slot[q - lo] = t | (what << 8);
+          ++q;
+        }
+        __syncthreads();
+        const uint32_t j = lo + t;
+        const int64_t pos = (int64_t)cur + j;
+        if (j < total && pos < cap) {
+          const uint32_t e = s_slot[t], what = e >> 8;
+          const int64_t src = row0 + (e & 0xffu);
+          const bool copy = what < XR_PASS;
+          out.ts[pos] = in.ts[src];
+          out.raw[pos] = copy ? tab->range_raw[what] : in.raw[src];
+          out.gidx[pos] = ((gbase + (uint64_t)src) << shift) | (copy ? (uint64_t)tab->range_pos[what] : 0ull);
+          if (sp.stream) out.stream[pos] = in.stream[src];
+          for (int c = 0; c < sp.ncols; ++c) {   // (uniform branches: the same columns for every thread)
+            if (sp.width[c] == 8) ((int64_t*)out.col[c])[pos] = ((const int64_t*)in.col[c])[src];
+            else if (sp.width[c] == 4) ((int32_t*)out.col[c])[pos] = ((const int32_t*)in.col[c])[src];
+            if (sp.nul[c]) out.nul[c][pos] = in.nul[c][src];
+          }
+        }
+        __syncthreads();
+      }
+      if (t == 0) s_cur[s] = cur + total;
+      __syncthreads();   // s_wtot and s_cur[s] are rewritten by the next shard / step
+    }
+  }
+}
+
 struct XSlices {
   uint64_t lo[MAX_GPUS + 1];   // global index of each slice's first row; [G] = the chunk's end
 };
@@ -416,8 +560,10 @@ struct XWant {
   int32_t width[SG_MAX_SELECT];   // 0: column not delivered
   int32_t nul[SG_MAX_SELECT];
 };
-__device__ __forceinline__ void xcopy_row(const XLay& a, int64_t i, const XLay& b, int64_t o, const XWant& w) {
-  ((uint64_t*)(b.base + b.off_trig))[o] = ((const uint64_t*)(a.base + a.off_trig))[i];
+// (shift: the delivered trigger is the event index, the internal one shifted down -- 0 without range partitions)
+__device__ __forceinline__ void xcopy_row(const XLay& a, int64_t i, const XLay& b, int64_t o, const XWant& w,
+                                          uint32_t shift) {
+  ((uint64_t*)(b.base + b.off_trig))[o] = ((const uint64_t*)(a.base + a.off_trig))[i] >> shift;
   if (w.ts) ((int64_t*)(b.base + b.off_ts))[o] = ((const int64_t*)(a.base + a.off_ts))[i];
   if (w.key) ((int32_t*)(b.base + b.off_key))[o] = ((const int32_t*)(a.base + a.off_key))[i];
   if (w.grp) ((uint32_t*)(b.base + b.off_grp))[o] = ((const uint32_t*)(a.base + a.off_grp))[i];
@@ -428,11 +574,11 @@ __device__ __forceinline__ void xcopy_row(const XLay& a, int64_t i, const XLay& 
   }
 }
 __global__ void k_xplace(XLay in, int64_t M, uint64_t slo, const uint32_t* __restrict__ off,
-                         const uint32_t* __restrict__ seg, XLay out, XWant w) {
+                         const uint32_t* __restrict__ seg, XLay out, XWant w, uint32_t shift) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M) return;
   const uint64_t t = ((const uint64_t*)(in.base + in.off_trig))[i] - slo;
-  xcopy_row(in, i, out, (int64_t)off[t] + (i - (int64_t)seg[t]), w);
+  xcopy_row(in, i, out, (int64_t)off[t] + (i - (int64_t)seg[t]), w, shift);
 }
 
 // ---- host side of the exchange ---------------------------------------------------------------------------------
@@ -484,6 +630,10 @@ void xrows_layout(XRows& r, int64_t cap, const XSpec& sp, bool gidx) {
 struct XGpu {
   XRows in[2], send[2];
   XBuf shard, bcnt, boff, scan_tmp, starts, bounds, mcnt, mseg, moff, mscan_tmp, l2g, nfg;
+  // range partitions: the descriptor's image and the shard table (uploaded once), hold masks and tile counts of a slice,
+  // and what the hold pass wants of a router that hands out label ids (every label known, minima unused)
+  XBuf rdev, rtab, rmask, rtile, rlk, rmins;
+  bool rtab_up = false;
   XBuf min[2], mo[2];
   int64_t min_cap[2] = {0, 0}, mo_cap[2] = {0, 0};
   int64_t l2g_n = 0;
@@ -512,9 +662,11 @@ struct XGpu {
       mo[p].release();
       min_cap[p] = mo_cap[p] = 0;
     }
-    for (XBuf* b : {&shard, &bcnt, &boff, &scan_tmp, &starts, &bounds, &mcnt, &mseg, &moff, &mscan_tmp, &l2g, &nfg})
+    for (XBuf* b : {&shard, &bcnt, &boff, &scan_tmp, &starts, &bounds, &mcnt, &mseg, &moff, &mscan_tmp, &l2g, &nfg, &rdev,
+                    &rtab, &rmask, &rtile, &rlk, &rmins})
       b->release();
     l2g_n = 0;
+    rtab_up = false;
     if (xs) hipStreamDestroy(xs);
     xs = nullptr;
     for (hipEvent_t* e : {ev_in, ev_scat, ev_sent, ev_rfree, ev_osent, ev_mfree, ev_d2h})
@@ -576,9 +728,21 @@ struct sg_node {
   KeyDict kd[MAX_GPUS];
   int64_t* draw[MAX_GPUS][2] = {};   // device raw-key slots
   int64_t draw_rows = 0;
-  std::vector<int32_t> l2g[MAX_GPUS];   // G > 1, device mode: shard-local id -> node-wide first-seen id
-  XGpu x[MAX_GPUS];                  // G > 1, device mode: the GPU-side shard exchange's buffers, streams, events
+  std::vector<int32_t> l2g[MAX_GPUS];   // exchange: shard-local id -> node-wide first-seen id
+  XGpu x[MAX_GPUS];                  // device mode, G > 1 or range partitions: the GPU-side shard exchange's buffers
   int64_t g_keys = 0;
+  // range partitions (sg_node_set_ranges): rows are routed on the GPUs inside the exchange, at any G
+  struct Ranges {
+    bool on = false;
+    sg_range_desc desc;
+    int depth = 0;
+    int rmax = 1;                    // the most ranges one stream has
+    uint32_t shift = 0;              // internal index = event index << shift | range position (2^shift >= rmax)
+    bool reads[SG_MAX_COLS] = {};    // batch columns the range conditions read
+    RrDev dev;
+    XrTab tab;
+    sg_range_stats stats = {};
+  } rng;
 };
 
 namespace {
@@ -692,6 +856,7 @@ struct Run {
   // per slice (G + 1 each, x_row), new keys' first global rows and the shard's key count before them; per step and
   // GPU the chunks past it (x_pass / x_wait); the chunks whose node-wide key ids are assigned
   XSpec xsp;
+  XSpec xsp_in;   // what is uploaded: xsp plus the columns only range conditions read
   std::vector<int64_t> xst, xpc, xkbase;
   std::vector<std::vector<uint64_t>> xnf;
   int64_t xstep[N_XSTEPS][MAX_GPUS] = {};
@@ -1411,7 +1576,20 @@ void merge_loop(Run& r) {
 }
 
 // ---- GPU-side shard exchange: the per-push pipeline (G > 1, device dictionary) -----------------------------------
-bool use_xchg(const sg_node& nd) { return nd.G > 1 && nd.ddict == 1; }
+bool use_xchg(const sg_node& nd) { return (nd.G > 1 || nd.rng.on) && nd.ddict == 1; }
+
+// the upload's columns: the exchanged ones and, with range partitions, those their conditions read
+XSpec xspec_in_of(const sg_node& nd, const sg_node_batch& b, const XSpec& sp) {
+  XSpec in = sp;
+  if (!nd.rng.on) return in;
+  for (int c = 0; c < nd.desc.n_cols; ++c) {
+    if (!nd.rng.reads[c]) continue;
+    if (!b.cols || !b.cols[c]) throw SgError(SG_EINVAL, "node batch is missing a column a range condition reads");
+    in.width[c] = sg_col_width(nd.desc.col_type[c]);
+    in.nul[c] = (b.nulls && b.nulls[c]) ? 1 : 0;
+  }
+  return in;
+}
 
 XSpec xspec_of(const sg_node& nd, const sg_node_batch& b) {
   const sg_nfa_desc& d = nd.desc;
@@ -1445,7 +1623,7 @@ void xcopy(void* dst, int ddev, const void* src, int sdev, size_t bytes, hipStre
 void x_upload(Run& r, int g, int64_t j) {
   sg_node& nd = r.nd;
   XGpu& X = nd.x[g];
-  const XSpec& sp = r.xsp;
+  const XSpec& sp = r.xsp_in;
   const int p = (int)(j & 1);
   int64_t a, e;
   x_slice(r, j, g, a, e);
@@ -1533,6 +1711,11 @@ void x_reserve(Run& r) {
   const int G = nd.G;
   const int64_t C = r.C, S = C / G + 1;
   const int64_t nblk = (S + XB_ROWS - 1) / XB_ROWS;
+  // range partitions: a row has up to R copies -- every buffer behind the scatter holds R times the rows, and the
+  // merge's per-trigger tables cover the slice in the internal index space (2^shift entries per row)
+  const int64_t R = nd.rng.on ? nd.rng.rmax : 1;
+  const int64_t MT = S << nd.rng.shift;
+  if (C * R >= (1ll << 30)) throw SgError(SG_EINVAL, "node chunk too large for its range copies (rows x ranges < 2^30)");
   for (int g = 0; g < G; ++g) {
     XGpu& X = nd.x[g];
     SgHandle& h = nd.h[g]->h;
@@ -1544,38 +1727,53 @@ void x_reserve(Run& r) {
       X.init = true;
     }
     for (int p = 0; p < 2; ++p) {
-      xrows_layout(X.in[p], S, sp, false);
-      xrows_layout(X.send[p], S, sp, true);
+      xrows_layout(X.in[p], S, r.xsp_in, false);
+      if (G > 1) xrows_layout(X.send[p], S * R, sp, true);   // (one shard: the scatter writes the receive slot itself)
     }
     X.shard.ensure((size_t)S);
     X.bcnt.ensure(4 * (size_t)(G * nblk + 1));
     X.boff.ensure(4 * (size_t)(G * nblk + 1));
     X.starts.ensure(4 * (MAX_GPUS + 1));
     X.bounds.ensure(8 * (MAX_GPUS + 1));
-    X.mcnt.ensure(4 * (size_t)(S + 1));
-    X.mseg.ensure(4 * (size_t)(S + 1));
-    X.moff.ensure(4 * (size_t)(S + 1));
+    X.mcnt.ensure(4 * (size_t)(MT + 1));
+    X.mseg.ensure(4 * (size_t)(MT + 1));
+    X.moff.ensure(4 * (size_t)(MT + 1));
     size_t tb = 0;
     HIPCHK(rocprim::exclusive_scan(nullptr, tb, X.bcnt.as<uint32_t>(), X.boff.as<uint32_t>(), (uint32_t)0,
                                    (size_t)(G * nblk + 1), rocprim::plus<uint32_t>(), h.stream));
     X.scan_tmp.ensure(tb);
     tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, X.mcnt.as<uint32_t>(), X.moff.as<uint32_t>(), (uint32_t)0, (size_t)(S + 1),
+    HIPCHK(rocprim::exclusive_scan(nullptr, tb, X.mcnt.as<uint32_t>(), X.moff.as<uint32_t>(), (uint32_t)0, (size_t)(MT + 1),
                                    rocprim::plus<uint32_t>(), h.stream));
     X.mscan_tmp.ensure(tb);
     for (int p = 0; p < 2; ++p) X.hstarts[p].ensure(8 * (MAX_GPUS + 1));
     X.hbounds.ensure(8 * (MAX_GPUS + 1));
-    // receive slots: a shard may get every row of a chunk
-    reserve_slots(nd, g, C, sp.stream != 0, true, [&](int c) { return sp.width[c] != 0; },
+    if (nd.rng.on) {
+      X.rmask.ensure(4 * (size_t)S);
+      X.rtile.ensure(8 * (size_t)((S + RR_TILE - 1) / RR_TILE + 1));
+      if (!X.rtab_up) {
+        X.rdev.ensure(sizeof(RrDev));
+        X.rtab.ensure(sizeof(XrTab));
+        X.rlk.ensure(4 * SG_MAX_RANGES);
+        X.rmins.ensure(8 * SG_MAX_RANGES);
+        HIPCHK(hipMemcpy(X.rdev.p, &nd.rng.dev, sizeof(RrDev), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(X.rtab.p, &nd.rng.tab, sizeof(XrTab), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(X.rlk.p, 0, 4 * SG_MAX_RANGES));      // every label "known": no first-holder minima
+        HIPCHK(hipMemset(X.rmins.p, 0, 8 * SG_MAX_RANGES));
+        X.rtab_up = true;
+      }
+    }
+    // receive slots: a shard may get every row (every copy) of a chunk
+    reserve_slots(nd, g, C * R, sp.stream != 0, true, [&](int c) { return sp.width[c] != 0; },
                   [&](int c) { return sp.nul[c] != 0; });
-    if (nd.draw_rows < C) regrow_slots(nd.draw[g], C);
+    if (nd.draw_rows < C * R) regrow_slots(nd.draw[g], C * R);
     HIPCHK(hipStreamSynchronize(h.stream));
     sg_egress_init(h);
-    const int64_t eb = (int64_t)sg_col_layout(h.desc, std::max<int64_t>(1, std::min<int64_t>(S, r.cap))).bytes;
+    const int64_t eb = (int64_t)sg_col_layout(h.desc, std::max<int64_t>(1, std::min<int64_t>(S * R, r.cap))).bytes;
     sg_stage_reserve(h, 0, eb);
     sg_stage_reserve(h, 1, eb);
   }
-  nd.draw_rows = std::max(nd.draw_rows, C);
+  nd.draw_rows = std::max(nd.draw_rows, C * R);
 }
 
 // merge input / output slot p of GPU g for m rows (waits for the slot's earlier users first)
@@ -1612,10 +1810,30 @@ void x_shard(Run& r, int g, const XChunk& c) {
   const int64_t n = c.n, nblk = (n + XB_ROWS - 1) / XB_ROWS;
   HIPCHK(hipStreamWaitEvent(h.stream, X.ev_in[p], 0));
   uint32_t* hst = X.hstarts[p].as<uint32_t>();
+  const bool ranges = nd.rng.on;
   if (n > 0) {
     HIPCHK(hipMemsetAsync(X.bcnt.as<uint32_t>() + G * nblk, 0, 4, h.stream));
-    hipLaunchKernelGGL(k_xcount, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c.raw, X.in[p].c.stream, n,
-                       (uint32_t)G, X.shard.as<uint8_t>(), X.bcnt.as<uint32_t>(), (uint32_t)nblk);
+    if (ranges) {   // hold masks of the slice's rows, then copies per (block, shard)
+      RrIn in;
+      memset(&in, 0, sizeof(in));
+      in.n = n;
+      in.ts = X.in[p].c.ts;
+      in.stream = X.in[p].c.stream;
+      SgCols cols;
+      for (int k = 0; k < SG_MAX_COLS; ++k) {
+        cols.col[k] = X.in[p].c.col[k];
+        cols.nul[k] = X.in[p].c.nul[k];
+      }
+      rr_launch_hold(nd.rng.depth, h.stream, (unsigned)((n + RR_TILE - 1) / RR_TILE), in, cols, X.rdev.as<RrDev>(),
+                     X.rlk.as<int32_t>(), X.rmask.as<uint32_t>(), X.rtile.as<int64_t>(),
+                     X.rmins.as<unsigned long long>());
+      hipLaunchKernelGGL(k_xrcount, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c.raw, X.in[p].c.stream,
+                         X.rmask.as<uint32_t>(), X.rtab.as<XrTab>(), n, (uint32_t)G, X.bcnt.as<uint32_t>(),
+                         (uint32_t)nblk);
+    } else {
+      hipLaunchKernelGGL(k_xcount, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c.raw, X.in[p].c.stream, n,
+                         (uint32_t)G, X.shard.as<uint8_t>(), X.bcnt.as<uint32_t>(), (uint32_t)nblk);
+    }
     HIPCHK(hipGetLastError());
     size_t tb = X.scan_tmp.bytes;
     HIPCHK(rocprim::exclusive_scan(X.scan_tmp.p, tb, X.bcnt.as<uint32_t>(), X.boff.as<uint32_t>(), (uint32_t)0,
@@ -1624,9 +1842,32 @@ void x_shard(Run& r, int g, const XChunk& c) {
                        X.starts.as<uint32_t>());
     HIPCHK(hipMemcpyAsync(hst, X.starts.p, 4 * (size_t)(G + 1), hipMemcpyDeviceToHost, h.stream));
     HIPCHK(hipStreamSynchronize(h.stream));
-    hipLaunchKernelGGL(k_xscatter, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c, X.send[p].c, r.xsp, n,
-                       r.b.base_index + (uint64_t)c.a, X.shard.as<uint8_t>(), X.boff.as<uint32_t>(), (uint32_t)nblk,
-                       (uint32_t)G);
+    if (ranges) {
+      // every store of the scatter lands below hst[G] (the scanned total); check it against the rows allocated first
+      const int64_t cap = G == 1 ? r.C * nd.rng.rmax : X.send[p].cap;
+      if ((int64_t)hst[G] > cap || (int64_t)hst[G] > n * nd.rng.rmax)
+        throw SgError(SG_EINVAL, "internal: range copies of a slice exceed its send buffer");
+      XCols dst = X.send[p].c;
+      if (G == 1) {   // one shard: straight into the slot kd_resolve and sg_push_view read
+        const SlotPtrs& sl = nd.dslot[g][p];
+        memset(&dst, 0, sizeof(dst));
+        dst.ts = (int64_t*)sl.ts;
+        dst.raw = nd.draw[g][p];
+        dst.gidx = (uint64_t*)sl.index;
+        dst.stream = (int32_t*)sl.stream;
+        for (int k = 0; k < r.xsp.ncols; ++k) {
+          dst.col[k] = sl.col[k];
+          dst.nul[k] = (uint8_t*)sl.nul[k];
+        }
+      }
+      hipLaunchKernelGGL(k_xrscatter, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c, dst, r.xsp, n,
+                         r.b.base_index + (uint64_t)c.a, nd.rng.shift, cap, X.rmask.as<uint32_t>(), X.rtab.as<XrTab>(),
+                         X.boff.as<uint32_t>(), (uint32_t)nblk, (uint32_t)G);
+    } else {
+      hipLaunchKernelGGL(k_xscatter, dim3((unsigned)nblk), dim3(256), 0, h.stream, X.in[p].c, X.send[p].c, r.xsp, n,
+                         r.b.base_index + (uint64_t)c.a, X.shard.as<uint8_t>(), X.boff.as<uint32_t>(), (uint32_t)nblk,
+                         (uint32_t)G);
+    }
     HIPCHK(hipGetLastError());
   } else {
     for (int s = 0; s <= G; ++s) hst[s] = 0;
@@ -1656,7 +1897,7 @@ bool x_send_rows(Run& r, int g, const XChunk& c) {
   HIPCHK(hipStreamWaitEvent(X.xs, X.ev_scat[p], 0));
   for (int s = 0; s < G; ++s) {
     const int64_t cnt = r.x_cnt(r.xst, j, g, s);
-    if (!cnt) continue;
+    if (!cnt || G == 1) continue;   // (one shard: the range scatter wrote the receive slot)
     int64_t ro = 0;
     for (int q = 0; q < g; ++q) ro += r.x_cnt(r.xst, j, q, s);
     const int64_t so = r.x_row(r.xst, j, g)[s];
@@ -1716,6 +1957,7 @@ bool x_compute(Run& r, int g, XChunk& c) {
   HIPCHK(hipEventRecord(X.ev_rfree[p], h.stream));
   r.x_pass(X_USED, g, j, [&] {
     nd.local_rows[g] += ns;
+    nd.rng.stats.copies += nd.rng.on ? ns : 0;
     if (r.w.key) {
       r.xnf[(size_t)(j * G + g)].assign(X.hnf.as<uint64_t>(), X.hnf.as<uint64_t>() + (mnew > 0 ? mnew : 0));
       r.xkbase[(size_t)(j * G + g)] = kbefore;
@@ -1786,7 +2028,7 @@ void x_stage_matches(Run& r, int g, XChunk& c) {
     for (int q = 0; q <= G; ++q) {
       int64_t qa, qe;
       x_slice(r, j, q < G ? q : G - 1, qa, qe);
-      xs.lo[q] = r.b.base_index + (uint64_t)(q < G ? qa : qe);
+      xs.lo[q] = (r.b.base_index + (uint64_t)(q < G ? qa : qe)) << nd.rng.shift;   // (the internal index space)
     }
     hipLaunchKernelGGL(k_xbounds, dim3(1), dim3(64), 0, h.stream, (const uint64_t*)(h.eg.stage[p] + L.off_trig), k, xs,
                        (uint32_t)G, X.bounds.as<int64_t>());
@@ -1870,11 +2112,14 @@ bool x_merge_deliver(Run& r, int g, const XChunk& c) {
     return true;
   }
   x_merge_room(nd, g, p, mg, true);
-  const uint64_t slo = r.b.base_index + (uint64_t)c.a;
+  // triggers are internal indices (event index << shift | range position): the tables cover the slice in that space
+  const uint32_t shift = nd.rng.shift;
+  const uint64_t slo = (r.b.base_index + (uint64_t)c.a) << shift;
+  const int64_t mt = c.n << shift;
   XRuns runs;
   runs.off[0] = 0;
   for (int s = 0; s < G; ++s) runs.off[s + 1] = runs.off[s] + r.x_cnt(r.xpc, j, s, g);
-  HIPCHK(hipMemsetAsync(X.mcnt.p, 0, 4 * (size_t)(c.n + 1), h.stream));
+  HIPCHK(hipMemsetAsync(X.mcnt.p, 0, 4 * (size_t)(mt + 1), h.stream));
   const ColLayout Li = sg_col_layout(nd.desc, X.min_cap[p]), Lo = sg_col_layout(nd.desc, X.mo_cap[p]);
   const XLay li = xlay(X.min[p].as<char>(), r.w, Li), lo = xlay(X.mo[p].as<char>(), r.w, Lo);
   hipLaunchKernelGGL(k_xmark, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream,
@@ -1883,10 +2128,10 @@ bool x_merge_deliver(Run& r, int g, const XChunk& c) {
   HIPCHK(hipGetLastError());
   size_t tb = X.mscan_tmp.bytes;
   HIPCHK(rocprim::exclusive_scan(X.mscan_tmp.p, tb, X.mcnt.as<uint32_t>(), X.moff.as<uint32_t>(), (uint32_t)0,
-                                 (size_t)(c.n + 1), rocprim::plus<uint32_t>(), h.stream));
+                                 (size_t)(mt + 1), rocprim::plus<uint32_t>(), h.stream));
   HIPCHK(hipStreamWaitEvent(h.stream, X.ev_d2h[p], 0));   // the output slot's last copies are done
   hipLaunchKernelGGL(k_xplace, dim3((unsigned)((mg + 255) / 256)), dim3(256), 0, h.stream, li, mg, slo,
-                     X.moff.as<uint32_t>(), X.mseg.as<uint32_t>(), lo, xwant(r.w, Lo));
+                     X.moff.as<uint32_t>(), X.mseg.as<uint32_t>(), lo, xwant(r.w, Lo), shift);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(X.ev_mfree[p], h.stream));
   HIPCHK(hipStreamWaitEvent(h.eg.d2h, X.ev_mfree[p], 0));
@@ -1912,6 +2157,9 @@ void x_loop(Run& r, int g) {
   sg_node& nd = r.nd;
   r.guarded([&] {
     HIPCHK(hipSetDevice(nd.dev[g]));
+    // one shard (range partitions): the trigger-row columns are filled on the host as in gpu_loop / fill_loop, by the
+    // delivered trigger -- the event index, whichever range's copy completed the match
+    const bool fill = nd.G == 1 && r.w.any_fill;
     XChunk c;
     for (c.j = 0; c.j < r.nch; ++c.j) {
       const double t0 = now_ms();
@@ -1922,6 +2170,10 @@ void x_loop(Run& r, int g) {
       x_slice(r, c.j, g, c.a, e);
       c.n = e - c.a;
       x_shard(r, g, c);
+      if (fill && c.j > 0) {   // the previous chunk's matches have landed: hand them to the host fill
+        HIPCHK(hipEventSynchronize(nd.x[g].ev_d2h[c.p ^ 1]));
+        r.publish([&] { r.delivered[0] = c.j; });
+      }
       if (!x_send_rows(r, g, c)) return;
       if (!x_compute(r, g, c)) return;
       if (r.w.key && !x_assign_ids(r, g, c)) return;
@@ -1933,11 +2185,13 @@ void x_loop(Run& r, int g) {
       r.publish([&] {
         r.t_gpu[g] += now_ms() - t0;
         if (g == 0) r.out_rows = c.out_before;
+        if (fill) r.dlv_end[0][c.j] = c.out_before;
       });
     }
     HIPCHK(hipStreamSynchronize(nd.h[g]->h.stream));
     HIPCHK(hipStreamSynchronize(nd.x[g].xs));
     HIPCHK(hipStreamSynchronize(nd.h[g]->h.eg.d2h));
+    if (fill) r.publish([&] { r.delivered[0] = r.nch; });
   });
 }
 
@@ -2013,13 +2267,21 @@ void run_push(sg_node& nd, const sg_node_batch& b, const sg_match_columns* out, 
     const bool dev_ok = nd.desc.partitioned && !need_clocks(nd.desc);
     nd.ddict = (dev_ok && nd.key_dict_mode != 1) ? 1 : 0;
   }
+  if (nd.rng.on) {
+    if (nd.ddict != 1) throw SgError(SG_EINVAL, "internal: range partitions without the device dictionary");
+    // every copy's internal index is (event index << shift | range position)
+    if (b.base_index + (uint64_t)b.n < b.base_index || ((b.base_index + (uint64_t)b.n) >> (64 - nd.rng.shift - 1)) != 0)
+      throw SgError(SG_EINVAL, "node: base_index too large for the range copies' internal index");
+  }
   Run r(nd, b, out, cap);
   const bool xchg = use_xchg(nd);
-  r.w = want_of(nd, b, out, !xchg);
-  // default chunks: ~16 per push (short pipeline fill and drain), 4M..25M rows each
+  r.w = want_of(nd, b, out, !xchg || nd.G == 1);
+  // default chunks: ~16 per push (short pipeline fill and drain), 4M..25M rows each (range partitions: divided by the
+  // most copies a row can have, which every buffer behind the scatter is sized for)
   r.C = nd.chunk_rows > 0 ? nd.chunk_rows
                           : std::max<int64_t>(1, std::min<int64_t>(b.n, std::max<int64_t>((int64_t)4 << 20,
-                                                                   std::min<int64_t>((int64_t)25 << 20, (b.n + 15) / 16))));
+                                                                   std::min<int64_t>((int64_t)25 << 20, (b.n + 15) / 16)) /
+                                                                            (nd.rng.on ? nd.rng.rmax : 1)));
   if (r.C >= (1ll << 30) - 1) throw SgError(SG_EINVAL, "node chunk too large (max 2^30-2 rows)");
   r.nch = (b.n + r.C - 1) / r.C;
   for (int s = 0; s < nd.G; ++s) r.dlv_end[s].assign((size_t)r.nch, 0);
@@ -2035,6 +2297,7 @@ void run_push(sg_node& nd, const sg_node_batch& b, const sg_match_columns* out, 
   if (xchg) {   // GPU-side shard exchange: one loop per GPU, no host route or merge
     const int G = nd.G;
     r.xsp = xspec_of(nd, b);
+    r.xsp_in = xspec_in_of(nd, b, r.xsp);
     r.xst.assign((size_t)(r.nch * G * (G + 1)), 0);
     r.xpc.assign((size_t)(r.nch * G * (G + 1)), 0);
     r.xkbase.assign((size_t)(r.nch * G), 0);
@@ -2042,6 +2305,7 @@ void run_push(sg_node& nd, const sg_node_batch& b, const sg_match_columns* out, 
     x_reserve(r);
     t1 = now_ms();
     for (int s = 0; s < G; ++s) th.push_back(tc.run([&r, s] { x_loop(r, s); }));
+    if (G == 1 && r.w.any_fill) th.push_back(tc.run([&r] { fill_loop(r); }));
   } else {
   reserve_all(r);
   t1 = now_ms();
@@ -2101,6 +2365,10 @@ void run_push(sg_node& nd, const sg_node_batch& b, const sg_match_columns* out, 
   st.h2d_bytes = r.h2d_bytes;
   st.d2h_bytes = r.d2h_bytes;
   for (int s = 0; s < nd.G; ++s) st.shard_rows[s] = nd.local_rows[s];
+  if (nd.rng.on) {
+    nd.rng.stats.rows += b.n;
+    nd.rng.stats.calls++;
+  }
   *n_out = r.out_rows;
 }
 
@@ -2229,6 +2497,7 @@ int sg_node_reset(sg_node* nd) {
   }
   nd->g_keys = 0;
   nd->ddict = -1;
+  memset(&nd->rng.stats, 0, sizeof(nd->rng.stats));   // (the ranges themselves stay)
   if (nd->router) sg_router_close(nd->router);
   nd->router = nullptr;
   const int x = sg_router_open(nd->G, nd->threads, &nd->router);
@@ -2264,7 +2533,65 @@ int sg_node_set_key_dict(sg_node* nd, int mode) {
     nd->err = "node: the device dictionary needs a partitioned query without playback timers";
     return SG_EUNSUPPORTED;
   }
+  if (mode == 1 && nd->rng.on) {
+    nd->err = "node: range partitions are routed on the GPUs and need the device dictionary";
+    return SG_EINVAL;
+  }
   nd->key_dict_mode = mode;
+  return SG_OK;
+}
+
+int sg_node_set_ranges(sg_node* nd, const sg_range_desc* d, const int64_t* label_raw) {
+  if (!nd) return SG_EINVAL;
+  try {
+    if (!d || !label_raw) throw SgError(SG_EINVAL, "node: null range descriptor or label keys");
+    if (nd->ddict >= 0)
+      throw SgError(SG_EINVAL, "node: ranges are set before the first push of a stream (or after sg_node_reset)");
+    if (nd->key_dict_mode == 1)
+      throw SgError(SG_EINVAL, "node: range partitions need the device dictionary (sg_node_set_key_dict 0 or 2)");
+    const int depth = rr_validate(*d);
+    const sg_nfa_desc& q = nd->desc;
+    if (d->n_cols != q.n_cols) throw SgError(SG_EINVAL, "node: the range descriptor's n_cols is not the query's");
+    for (int c = 0; c < d->n_cols; ++c)
+      if (d->col_type[c] != q.col_type[c] || d->col_stream[c] != q.col_stream[c])
+        throw SgError(SG_EINVAL, "node: the range descriptor's columns are not the query's");
+    if (!q.partitioned) throw SgError(SG_EUNSUPPORTED, "node: range partitions need a partitioned query");
+    if (need_clocks(q))
+      throw SgError(SG_EUNSUPPORTED, "node: queries with playback timers route their ranges on the host");
+    sg_node::Ranges& R = nd->rng;
+    R.desc = *d;
+    R.depth = depth;
+    R.dev = rr_dev_image(*d);
+    R.dev.playback = 0;   // no timers: a row that holds no range changes no runtime and is dropped
+    memset(&R.tab, 0, sizeof(R.tab));
+    memset(R.reads, 0, sizeof(R.reads));
+    rr_for_each_read_col(*d, [&](int c) { R.reads[c] = true; });
+    uint32_t per_stream[SG_MAX_STREAMS] = {};
+    R.rmax = 1;
+    for (int k = 0; k < d->n_ranges; ++k) {
+      const int s = d->range_stream[k];
+      const int64_t raw = label_raw[d->range_label[k]];
+      R.tab.ranged_streams |= 1u << s;
+      R.tab.range_raw[k] = raw;
+      R.tab.range_pos[k] = per_stream[s]++;
+      R.tab.shard_mask[s][sgr::mix64((uint64_t)raw) % (uint64_t)nd->G] |= 1u << k;
+      R.rmax = std::max<int>(R.rmax, (int)per_stream[s]);
+    }
+    R.shift = 0;
+    while ((1 << R.shift) < R.rmax) ++R.shift;
+    memset(&R.stats, 0, sizeof(R.stats));
+    for (int g = 0; g < nd->G; ++g) nd->x[g].rtab_up = false;
+    R.on = true;
+  } catch (SgError& e) {
+    nd->err = e.msg;
+    return e.code;
+  }
+  return SG_OK;
+}
+
+int sg_node_range_stats_get(const sg_node* nd, sg_range_stats* st) {
+  if (!nd || !st) return SG_EINVAL;
+  *st = nd->rng.stats;
   return SG_OK;
 }
 
