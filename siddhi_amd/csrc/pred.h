@@ -99,10 +99,19 @@ __device__ __forceinline__ bool cmp_op(D a, D b) {
   if (OP == 4) return a < b;
   return a <= b;
 }
+// A null operand: `!=` is true and every other compare false (sg_cmp; NotEqualCompareConditionExpressionExecutor.java:37,
+// CompareConditionExpressionExecutor.java:39-43) -- unless the column is the closed form's compared value (null_ne
+// false), whose null rows are never candidates (eval_row).  `in`: the row exists and is of A's stream.
+template <int OP>
+__device__ __forceinline__ bool null_rule(bool ok, bool in, bool null_ne, const uint8_t* __restrict__ nul, int64_t r) {
+  if (OP == 1 && null_ne) return (in && !ok) ? nul[r] != 0 : ok;
+  return ok ? !nul[r] : false;
+}
 constexpr int PRED_TILES_PER_WAVE = 4;
 template <class V, class D, int OP>
 __global__ void __launch_bounds__(256) k_pred_simple(int64_t n, D c, const V* __restrict__ col,
-                                                     const uint8_t* __restrict__ nul, uint64_t* __restrict__ cand_m) {
+                                                     const uint8_t* __restrict__ nul, bool null_ne,
+                                                     uint64_t* __restrict__ cand_m) {
   constexpr int U = PRED_TILES_PER_WAVE;
   const int lane = threadIdx.x & 63;
   const int64_t ntiles = (n + 255) >> 8;
@@ -131,8 +140,9 @@ __global__ void __launch_bounds__(256) k_pred_simple(int64_t n, D c, const V* __
     uint64_t mine = 0;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      bool ok = (i + s < n) && cmp_op<OP, D>((D)xs[s], c);
-      if (nul && ok) ok = !nul[i + s];
+      const bool in = i + s < n;
+      bool ok = in && cmp_op<OP, D>((D)xs[s], c);
+      if (nul) ok = null_rule<OP>(ok, in, null_ne, nul, i + s);
       const uint64_t m = __ballot(ok);
       if (lane == s) mine = m;
     }
@@ -144,8 +154,9 @@ __global__ void __launch_bounds__(256) k_pred_simple(int64_t n, D c, const V* __
 // compared value no nulls) -- the stream column is streamed with 16-B loads as well
 template <class V, class D, int OP>
 __global__ void __launch_bounds__(256) k_pred_simple_s(int64_t n, D c, const V* __restrict__ col,
-                                                       const uint8_t* __restrict__ nul, const int32_t* __restrict__ stream,
-                                                       int32_t sa, int32_t sb, uint64_t* __restrict__ cand_m,
+                                                       const uint8_t* __restrict__ nul, bool null_ne,
+                                                       const int32_t* __restrict__ stream, int32_t sa, int32_t sb,
+                                                       uint64_t* __restrict__ cand_m,
                                                        uint64_t* __restrict__ cons_m) {
   const int lane = threadIdx.x & 63;
   const int64_t ntiles = (n + 255) >> 8;
@@ -174,8 +185,9 @@ __global__ void __launch_bounds__(256) k_pred_simple_s(int64_t n, D c, const V* 
   uint64_t ma = 0, mb = 0;
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    bool ok = (i + s < n) && ts[s] == sa && cmp_op<OP, D>((D)xs[s], c);
-    if (nul && ok) ok = !nul[i + s];
+    const bool in = (i + s < n) && ts[s] == sa;
+    bool ok = in && cmp_op<OP, D>((D)xs[s], c);
+    if (nul) ok = null_rule<OP>(ok, in, null_ne, nul, i + s);
     const uint64_t a = __ballot(ok);
     const uint64_t b = __ballot((i + s < n) && ts[s] == sb);
     if (lane == s) { ma = a; mb = b; }
@@ -187,12 +199,13 @@ __global__ void __launch_bounds__(256) k_pred_simple_s(int64_t n, D c, const V* 
 }
 
 template <class V, class D>
-static void launch_pred_simple_s(int op, int64_t n, D c, const V* col, const uint8_t* nul, const int32_t* stream,
-                                 int sa, int sb, uint64_t* cand_m, uint64_t* cons_m, hipStream_t st) {
+static void launch_pred_simple_s(int op, int64_t n, D c, const V* col, const uint8_t* nul, bool null_ne,
+                                 const int32_t* stream, int sa, int sb, uint64_t* cand_m, uint64_t* cons_m,
+                                 hipStream_t st) {
   const int64_t ntiles = (n + 255) >> 8;
   const dim3 grd((unsigned)std::max<int64_t>(1, (ntiles + 3) / 4)), blk(256);
-#define SG_PRED_S(OPV) hipLaunchKernelGGL((k_pred_simple_s<V, D, OPV>), grd, blk, 0, st, n, c, col, nul, stream, sa, sb, \
-                                          cand_m, cons_m)
+#define SG_PRED_S(OPV) hipLaunchKernelGGL((k_pred_simple_s<V, D, OPV>), grd, blk, 0, st, n, c, col, nul, null_ne, stream, \
+                                          sa, sb, cand_m, cons_m)
   switch (op) {
     case 0: SG_PRED_S(0); break;
     case 1: SG_PRED_S(1); break;
@@ -205,18 +218,18 @@ static void launch_pred_simple_s(int op, int64_t n, D c, const V* col, const uin
 }
 
 template <class V, class D>
-static void launch_pred_simple(int op, int64_t n, D c, const V* col, const uint8_t* nul, uint64_t* cand_m,
-                               hipStream_t st) {
+static void launch_pred_simple(int op, int64_t n, D c, const V* col, const uint8_t* nul, bool null_ne,
+                               uint64_t* cand_m, hipStream_t st) {
   const int64_t ntiles = (n + 255) >> 8;
   const int64_t waves = (ntiles + PRED_TILES_PER_WAVE - 1) / PRED_TILES_PER_WAVE;
   const dim3 grd((unsigned)std::max<int64_t>(1, (waves + 3) / 4)), blk(256);
   switch (op) {
-    case 0: hipLaunchKernelGGL((k_pred_simple<V, D, 0>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
-    case 1: hipLaunchKernelGGL((k_pred_simple<V, D, 1>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
-    case 2: hipLaunchKernelGGL((k_pred_simple<V, D, 2>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
-    case 3: hipLaunchKernelGGL((k_pred_simple<V, D, 3>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
-    case 4: hipLaunchKernelGGL((k_pred_simple<V, D, 4>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
-    default: hipLaunchKernelGGL((k_pred_simple<V, D, 5>), grd, blk, 0, st, n, c, col, nul, cand_m); break;
+    case 0: hipLaunchKernelGGL((k_pred_simple<V, D, 0>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
+    case 1: hipLaunchKernelGGL((k_pred_simple<V, D, 1>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
+    case 2: hipLaunchKernelGGL((k_pred_simple<V, D, 2>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
+    case 3: hipLaunchKernelGGL((k_pred_simple<V, D, 3>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
+    case 4: hipLaunchKernelGGL((k_pred_simple<V, D, 4>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
+    default: hipLaunchKernelGGL((k_pred_simple<V, D, 5>), grd, blk, 0, st, n, c, col, nul, null_ne, cand_m); break;
   }
 }
 
@@ -265,6 +278,7 @@ static void launch_pred(const sg_nfa_desc& d, const PredArgs& pa, const int32_t*
   bool simple = pa.cons_all && !stream && pa.s_a == 0 && simple_prog(d, pa.prog_a_off, pa.prog_a_len, sp) &&
                 (pa.val_col_a < 0 || sp.s_col == pa.val_col_a) && (((uintptr_t)cols.col[sp.s_col]) & 15) == 0;
   const dim3 blk(256);
+  const bool null_ne = pa.val_col_a < 0;   // (no compared-value column: a null row passes `!=`, as in the VM)
   // several streams: the same pass with the stream column when B's consumers are just B's stream's rows
   if (!simple && stream && cons_m && pa.prog_b_len == 0 && pa.val_col_b >= 0 && !cols.nul[pa.val_col_b] &&
       simple_prog(d, pa.prog_a_off, pa.prog_a_len, sp) && (pa.val_col_a < 0 || sp.s_col == pa.val_col_a) &&
@@ -275,10 +289,12 @@ static void launch_pred(const sg_nfa_desc& d, const PredArgs& pa, const int32_t*
     const uint8_t* nul = cols.nul[sp.s_col];
     if (sp.s_dom == 1) {
       float c = (sp.s_ctype == SG_T_FLOAT || sp.s_ctype == SG_T_DOUBLE) ? (float)cv.d : (float)cv.i;
-      launch_pred_simple_s<float, float>(sp.s_op, n, c, colp, nul, stream, pa.s_a, pa.s_b, cand_m, cons_m, st);
+      launch_pred_simple_s<float, float>(sp.s_op, n, c, colp, nul, null_ne, stream, pa.s_a, pa.s_b, cand_m, cons_m,
+                                          st);
     } else {
       double c = (sp.s_ctype == SG_T_FLOAT || sp.s_ctype == SG_T_DOUBLE) ? cv.d : (double)cv.i;
-      launch_pred_simple_s<float, double>(sp.s_op, n, c, colp, nul, stream, pa.s_a, pa.s_b, cand_m, cons_m, st);
+      launch_pred_simple_s<float, double>(sp.s_op, n, c, colp, nul, null_ne, stream, pa.s_a, pa.s_b, cand_m, cons_m,
+                                          st);
     }
     return;
   }
@@ -290,21 +306,21 @@ static void launch_pred(const sg_nfa_desc& d, const PredArgs& pa, const int32_t*
     if (sp.s_dom == 1) {
       float c = (sp.s_ctype == SG_T_FLOAT || sp.s_ctype == SG_T_DOUBLE) ? (float)cv.d : (float)cv.i;
       if (sp.s_type == SG_T_FLOAT)
-        launch_pred_simple<float, float>(sp.s_op, n, c, (const float*)colp, nul, cand_m, st);
+        launch_pred_simple<float, float>(sp.s_op, n, c, (const float*)colp, nul, null_ne, cand_m, st);
       else
-        launch_pred_simple<int32_t, float>(sp.s_op, n, c, (const int32_t*)colp, nul, cand_m, st);
+        launch_pred_simple<int32_t, float>(sp.s_op, n, c, (const int32_t*)colp, nul, null_ne, cand_m, st);
     } else if (sp.s_dom == 2) {
       double c = (sp.s_ctype == SG_T_FLOAT || sp.s_ctype == SG_T_DOUBLE) ? cv.d : (double)cv.i;
       if (sp.s_type == SG_T_FLOAT)
-        launch_pred_simple<float, double>(sp.s_op, n, c, (const float*)colp, nul, cand_m, st);
+        launch_pred_simple<float, double>(sp.s_op, n, c, (const float*)colp, nul, null_ne, cand_m, st);
       else
-        launch_pred_simple<int32_t, double>(sp.s_op, n, c, (const int32_t*)colp, nul, cand_m, st);
+        launch_pred_simple<int32_t, double>(sp.s_op, n, c, (const int32_t*)colp, nul, null_ne, cand_m, st);
     } else {
       int64_t c = (sp.s_ctype == SG_T_FLOAT || sp.s_ctype == SG_T_DOUBLE) ? (int64_t)cv.d : cv.i;
       if (sp.s_type == SG_T_FLOAT)
         simple = false;   // integral domain on a float column: leave it to the VM's conversions
       else
-        launch_pred_simple<int32_t, int64_t>(sp.s_op, n, c, (const int32_t*)colp, nul, cand_m, st);
+        launch_pred_simple<int32_t, int64_t>(sp.s_op, n, c, (const int32_t*)colp, nul, null_ne, cand_m, st);
     }
   }
   if (!simple) {

@@ -1,5 +1,7 @@
 """GPU parity for every code path of the closed-form every->next walker (siddhi_amd/csrc/walk.h, driven by engine_impl.h):
-the monotone-stack and scanned-list pending lists, all four compare operators, all four value types,
+the monotone-stack and scanned-list pending lists, all four compare operators (FLOAT prices), the INT,
+LONG and DOUBLE instantiations with `>` over values in [0, 1000) (test_value_types;
+test_closed_form_values.py runs all four types through every operator and route with edge values),
 the HBM-list overflow path (pending list deeper than the LDS ring, and units spanning > 2^31 ms), null
 handling of compared and projected attributes, and multi-push carry in each mode.  Every case is checked
 bit-for-bit against the CPU oracle on the same rows, and asserts that the lowering picked the closed form
