@@ -255,6 +255,10 @@ typedef struct sg_timing {
 
 typedef struct sg_handle sg_handle;
 
+/* SG_EINVAL for a malformed descriptor; SG_EUNSUPPORTED for a state filter, select, having or shape program that
+ * holds an unknown opcode or needs more than 16 operand-stack entries (the device VM's stack; the reference's executor
+ * trees have no such limit).  Both are decided before anything runs on the device; on failure *out still receives a
+ * handle that only sg_last_error and sg_close accept. */
 int sg_open(int hip_device, const sg_nfa_desc* nfa, const sg_options* opt, sg_handle** out);
 int sg_push(sg_handle* h, const sg_batch* b);
 int sg_advance_time(sg_handle* h, int64_t now, uint64_t trigger_index);

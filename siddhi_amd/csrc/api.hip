@@ -140,6 +140,22 @@ static void validate(const sg_nfa_desc* d) {
     if (st.stream < 0 || st.stream >= d->n_streams) throw SgError(SG_EINVAL, "state stream out of range");
     if (st.prog_off < 0 || st.prog_off + st.prog_len > d->code_len) throw SgError(SG_EINVAL, "bad program range");
   }
+  // every evaluator but k_pred runs its programs on the default 16-entry stack (sg_run); an unknown opcode's
+  // 1 << 30 is refused with them
+  auto too_deep = [&](int off, int len) { return len > 0 && sg_prog_depth(d->code + off, len) > SG_VM_STACK; };
+  for (int s = 0; s < d->n_states; ++s)
+    if (too_deep(d->states[s].prog_off, d->states[s].prog_len))
+      throw SgError(SG_EUNSUPPORTED, "state filter program deeper than the VM stack");
+  for (int k = 0; k < d->n_out; ++k)
+    if (too_deep(d->out_off[k], d->out_len[k]))
+      throw SgError(SG_EUNSUPPORTED, "select program deeper than the VM stack");
+  if (too_deep(d->having_off, d->having_len)) throw SgError(SG_EUNSUPPORTED, "having program deeper than the VM stack");
+  if (d->shape_prog_len > 0) {   // the closed forms' local conjuncts of the second state
+    if (d->shape_prog_off < 0 || d->shape_prog_off + d->shape_prog_len > d->code_len)
+      throw SgError(SG_EINVAL, "bad shape program range");
+    if (too_deep(d->shape_prog_off, d->shape_prog_len))
+      throw SgError(SG_EUNSUPPORTED, "shape program deeper than the VM stack");
+  }
   for (int r = 0; r < d->n_ret; ++r)
     if (d->ret_col[r] < 0 || d->ret_col[r] >= d->n_cols) throw SgError(SG_EINVAL, "retained column out of range");
   int timed = 0;

@@ -267,6 +267,27 @@ def math_type(lt: str, rt: str) -> str:
 D_I64, D_F32, D_F64, D_ID = 0, 1, 2, 3
 
 MAX_STATES, MAX_STREAMS, MAX_SELECT, MAX_RET, MAX_CODE = 16, 16, 32, 16, 512
+VM_STACK = 16      # SG_VM_STACK (csrc/sg_device.h): operand-stack entries of the device VM
+
+_OP_WIDTH = {OP_VAR: (5, 1), OP_CONST: (3, 1), OP_CMP: (3, -1), OP_MATH: (3, -1), OP_AND: (1, -1), OP_OR: (1, -1),
+             OP_NOT: (1, 0), OP_ISNULL: (1, 0)}     # opcode -> (words, change of the stack depth)
+
+
+def prog_depth(prog) -> int:
+    """Largest operand-stack depth of a postfix program (csrc/sg_device.h sg_prog_depth)."""
+    sp = mx = pc = 0
+    while pc < len(prog):
+        w, d = _OP_WIDTH[prog[pc]]
+        pc, sp = pc + w, sp + d
+        mx = max(mx, sp)
+    return mx
+
+
+def _check_depth(prog, clause: str):
+    """The device VM evaluates on a fixed stack (the reference's executor trees have no such limit)."""
+    d = prog_depth(prog)
+    if d > VM_STACK:
+        raise LoweringError(f"{clause}: expression needs an operand stack of {d}, the engine's VM has {VM_STACK}")
 
 
 @dataclass
@@ -671,6 +692,11 @@ class _FlatBuilder:
             out_progs, out_types = [], []
         if len(select) > MAX_SELECT or len(q.select) > MAX_SELECT:
             raise LoweringError("too many select attributes")
+        for s, st in enumerate(self.states):
+            _check_depth(st.prog, f"filter of state {s} ({st.ref or self.ctx.stream_ids[st.stream]})")
+        for oa, w in zip(q.select, out_progs):
+            _check_depth(w, f"select attribute {oa.rename}")
+        _check_depth(having_prog, "having")
         nfa = FlatNFA(self.stype, within, 1 if self.ctx.app.playback else 0, 1 if self.ctx.partitioned else 0,
                       self.states, receivers, order, ro, uo, start_ids, self.retained, select,
                       column_layout(self.ctx))

@@ -3,9 +3,9 @@
 The reference's QuerySelector evaluates `select` through the math executors
 (C/executor/math/{add,subtract,multiply,divide,mod}/*ExpressionExecutor{Int,Long,Float,Double}.java), with the
 result type from ExpressionParser.parseArithmeticOperationResultType (C/util/parser/ExpressionParser.java:1413-1431).
-CPU tests pin the oracle's arithmetic to an independent Python restatement of those executors (Java int/long
-wrap, truncating division, dividend-signed remainder, null on a null operand or a zero divisor, binary32 float
-arithmetic); GPU tests check the select pass (k_select over every engine route) bit-exact against the oracle.
+CPU tests pin the oracle's arithmetic to an independent Python restatement of those executors (select_ref._jmath:
+Java int/long wrap, truncating division, dividend-signed remainder, null on a null operand or a zero divisor, binary32
+float arithmetic); GPU tests check the select pass (k_select over every engine route) bit-exact against the oracle.
 No reference test exercises these edge values, so the Python restatement is the pin ("parity unpinned" against
 reference fixtures for this row)."""
 import math
@@ -15,6 +15,7 @@ import pytest
 
 from oracle import OracleEngine
 from parity_util import assert_same, dense_first_seen, run_engine, synth_batch
+from select_ref import _jmath
 from siddhi_amd import lowering as L
 from siddhi_amd import synth
 from siddhi_amd.runtime import Batch, QueryCallback, SiddhiAppCreationException, SiddhiManager
@@ -38,48 +39,6 @@ EDGE_ROWS = [
     (-7, -3, -3.4e38, -1e308),
     (13, -4, 7.25, -5.5),
 ]
-
-
-# ---- independent restatement of the Java executors (test infrastructure)
-def _wrap(x, bits):
-    m = 1 << bits
-    x %= m
-    return x - m if x >= m >> 1 else x
-
-
-def _jdiv(a, b):
-    q = abs(a) // abs(b)
-    return q if (a >= 0) == (b >= 0) else -q
-
-
-def _jmath(op, a, b, t):
-    if a is None or b is None:
-        return None
-    if t in ("INT", "LONG"):
-        bits = 32 if t == "INT" else 64
-        a, b = int(a), int(b)
-        if op in "/%" and b == 0:
-            return None
-        r = {"+": a + b, "-": a - b, "*": a * b}.get(op)
-        if op == "/":
-            r = _jdiv(a, b)
-        elif op == "%":
-            r = a - b * _jdiv(a, b)
-        return _wrap(r, bits)
-    if t == "FLOAT":
-        x, y = np.float32(a), np.float32(b)
-        if op in "/%" and y == 0:
-            return None
-        with np.errstate(all="ignore"):
-            r = {"+": x + y, "-": x - y, "*": x * y, "/": x / y}.get(op) if op != "%" else np.fmod(x, y)
-        return float(np.float32(r))
-    x, y = float(a), float(b)
-    if op in "/%" and y == 0:
-        return None
-    with np.errstate(all="ignore"):
-        r = {"+": x + y, "-": x - y, "*": x * y, "/": np.float64(x) / np.float64(y)}.get(op) \
-            if op != "%" else np.fmod(np.float64(x), np.float64(y))
-    return float(r)
 
 
 def _expected_edge():

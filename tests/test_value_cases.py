@@ -73,7 +73,7 @@ def test_every_constant_passes_some_rows_and_fails_some():
 
 def test_depth_cases_hit_every_register_stack():
     for case, (lo, hi) in zip(V.DEPTH, V.DEPTH_BUCKETS):
-        d = V.prog_depth(L.lower(V._context(case.app)).states[0].prog)
+        d = L.prog_depth(L.lower(V._context(case.app)).states[0].prog)
         assert lo < d <= hi, (case.name, d)
         n = len(V.reference(case))
         assert V.PRED_N // 20 < n < V.PRED_N - V.PRED_N // 20, (case.name, n)

@@ -385,18 +385,6 @@ def depth_cases() -> List[Case]:
     return [_pred(f"depth-{k}", "filter", q_p1("INT", nested(k)), "INT", "or", null_frac=0.05) for k in DEPTH_COMPARES]
 
 
-def prog_depth(prog) -> int:
-    """largest operand-stack depth of a postfix program (csrc/sg_device.h sg_prog_depth, restated)"""
-    width = {L.OP_VAR: (5, 1), L.OP_CONST: (3, 1), L.OP_CMP: (3, -1), L.OP_MATH: (3, -1), L.OP_AND: (1, -1),
-             L.OP_OR: (1, -1), L.OP_NOT: (1, 0), L.OP_ISNULL: (1, 0)}
-    sp = mx = pc = 0
-    while pc < len(prog):
-        w, d = width[prog[pc]]
-        pc, sp = pc + w, sp + d
-        mx = max(mx, sp)
-    return mx
-
-
 CLOSED = closed_form_cases()
 PRED = predicate_cases()
 DEPTH = depth_cases()
