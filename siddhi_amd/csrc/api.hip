@@ -800,7 +800,7 @@ int sg_close(sg_handle* hh) {
 }
 
 // ---- snapshot / restore -------------------------------------------------------------------------
-static const char SNAP_MAGIC[8] = {'S', 'G', 'S', 'N', 'A', 'P', '0', '3'};   // 03: sequence-lane state layout recorded
+static const char SNAP_MAGIC[8] = {'S', 'G', 'S', 'N', 'A', 'P', '0', '4'};   // 04: the per-key machine's playback clock recorded
 
 // Fingerprint of everything the persisted state's meaning depends on: the lowered query and the engine
 // route (closed form or general machine).  Field-wise, so struct padding never enters it.
@@ -882,7 +882,10 @@ int sg_restore(sg_handle* hh, const void* buf, size_t size) {
   return guard(hh, [&] {
     HIPCHK(hipSetDevice(h.device));
     HIPCHK(hipStreamSynchronize(h.stream));
-    h.bump_gen();   // from here on the state changes (or is reset on error)
+    // From here on the state changes.  A throw below leaves it half applied (the error is recorded, nothing is rolled
+    // back): the caller resets the handle before using it again, as the header says; sg_reset makes every such state
+    // a fresh one.
+    h.bump_gen();
     SnapR r{(const char*)buf, (const char*)buf + size};
     if (memcmp(r.take(8), SNAP_MAGIC, 8) != 0) throw SgError(SG_EINVAL, "not a siddhi_gpu snapshot");
     if (r.pod<int32_t>() != SG_ABI_VERSION) throw SgError(SG_EINVAL, "snapshot ABI version mismatch");
@@ -893,6 +896,7 @@ int sg_restore(sg_handle* hh, const void* buf, size_t size) {
     if (kind < 0 || kind > 4 || (h.state_kind && kind && h.state_kind != kind))
       throw SgError(SG_EINVAL, "snapshot engine kind does not match the handle");
     h.out.n = 0;
+    h.ts_max_seen = INT64_MIN;   // as sg_reset leaves it: what this handle pushed before says nothing about the blob's stream
     sg_every_next_reset(&h);
     sg_every_absent_reset(&h);
     sg_general_reset(&h);

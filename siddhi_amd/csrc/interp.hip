@@ -831,6 +831,7 @@ void sg_general_snapshot(SgHandle* h, SnapW& w) {
   const int32_t route = (gs && gs->pp && sg_partial_active(gs->pp) && h->opt.partial_lanes >= 0) ? 1 : 0;   // 1: partial lanes' carried rows
   w.pod(route);
   w.pod(gs ? gs->max_ts : (int64_t)INT64_MIN);
+  w.pod(gs ? gs->clock : (int64_t)0);   // the playback clock absence timers fire on (run_machine: na.clock0)
   if (route) {
     sg_partial_snapshot(h, gs->pp, w);
     return;
@@ -851,11 +852,13 @@ void sg_general_restore(SgHandle* h, SnapR& r) {
   }
   const int32_t route = r.pod<int32_t>();
   const int64_t max_ts = r.pod<int64_t>();
+  const int64_t clock = r.pod<int64_t>();
   if (route != 0 && route != 1) throw SgError(SG_EINVAL, "snapshot: bad general-route marker");
   if (route == 1) {
     if (!gs->pp || h->opt.partial_lanes < 0) throw SgError(SG_EINVAL, "snapshot: taken on the partial-lane route");
     sg_partial_restore(h, gs->pp, r);
     gs->max_ts = max_ts;
+    gs->clock = clock;
       // the machine's per-key runtimes from before the restore (a fallback taken earlier) are stale: a later fallback
     // rebuilds them from the restored carried rows alone
     if (gs->arena) HIPCHK(hipMemsetAsync(gs->arena, 0, (size_t)gs->keys_alloc * gs->geo.key_words * 4, st));
@@ -864,6 +867,7 @@ void sg_general_restore(SgHandle* h, SnapR& r) {
   }
   if (gs->pp) sg_partial_deactivate(gs->pp);
   gs->max_ts = max_ts;
+  gs->clock = clock;
   const int64_t keys = r.pod<int64_t>();
   if (keys < 0 || keys > (1ll << 31)) throw SgError(SG_EINVAL, "snapshot: bad key count");
   if (gs->arena) HIPCHK(hipMemsetAsync(gs->arena, 0, (size_t)gs->keys_alloc * gs->geo.key_words * 4, st));
