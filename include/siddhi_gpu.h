@@ -292,6 +292,42 @@ int sg_snapshot(sg_handle* h, void* buf, size_t cap, size_t* size);
 int sg_restore(sg_handle* h, const void* buf, size_t size);
 int sg_close(sg_handle* h);
 const char* sg_last_error(const sg_handle* h);
+
+/* ---- Attribute aggregators and group by (QuerySelector.processGroupBy / processNoGroupBy over attribute aggregators,
+ * C/query/selector/QuerySelector.java:125-216; C/query/selector/attribute/aggregator/{Count,Sum,Avg,Min,Max}
+ * AttributeAggregator.java; GroupByKeyGenerator.constructEventKey, C/query/selector/GroupByKeyGenerator.java:63-73).
+ * An aggregate output column k of the handle's query (kind[k] != SG_AGG_NONE) is fed, per match in delivery order, the
+ * value of its select program (sg_nfa_desc.out_off[k]: the aggregator's argument, of type arg_type[k]) and delivers
+ * the aggregator's running value (res_type[k], which must be sg_nfa_desc.out_type[k]); `having` sees the aggregated
+ * columns, and a match it drops has still updated its aggregators.  State is kept per partition key (partitioned
+ * queries) and, inside it, per group-by value tuple: two values are one group iff their Java strings are equal (-0.0
+ * and 0.0 apart, every NaN one group, null a group of its own, strings by dictionary id).  Group-by program g is the
+ * postfix program code[group_off[g] .. +group_len[g]) over the n_select projected slots (SG_OP_VAR word 3 = slot).
+ * The state is cleared by sg_reset and travels in sg_snapshot / sg_restore. */
+#define SG_AGG_ABI_VERSION 1
+#define SG_MAX_AGG 8          /* aggregate output columns per query */
+#define SG_MAX_GROUP_BY 4     /* group-by attributes per query */
+#define SG_AGG_MAX_CODE 64
+#define SG_AGG_NONE 0         /* a plain output column */
+#define SG_AGG_COUNT 1
+#define SG_AGG_SUM 2
+#define SG_AGG_AVG 3
+#define SG_AGG_MIN 4
+#define SG_AGG_MAX 5
+typedef struct sg_agg_desc {
+  int32_t abi_version;                  /* SG_AGG_ABI_VERSION */
+  int32_t n_out;                        /* the query's sg_nfa_desc.n_out */
+  int32_t kind[SG_MAX_SELECT], arg_type[SG_MAX_SELECT], res_type[SG_MAX_SELECT];
+  int32_t n_group;
+  int32_t group_type[SG_MAX_GROUP_BY], group_off[SG_MAX_GROUP_BY], group_len[SG_MAX_GROUP_BY];
+  int32_t code_len;
+  int64_t code[SG_AGG_MAX_CODE];
+} sg_agg_desc;
+/* Valid once, after sg_open and before the first push.  SG_EINVAL: a bad version or count (n_out that is not the
+ * query's or zero, no aggregate column or more than SG_MAX_AGG, n_group outside [0, SG_MAX_GROUP_BY], a bad kind, type
+ * or program range), a second call, or a call after a push; SG_EUNSUPPORTED: a group-by program deeper than the VM
+ * stack.  A refused call leaves the handle as it was. */
+int sg_set_aggregates(sg_handle* h, const sg_agg_desc* a);
 /* Host partition router (router.cpp): replaces the per-event key lookup of PartitionStreamReceiver.receive /
  * PartitionRuntime.cloneIfNotExist (C/partition/PartitionStreamReceiver.java:80-275,
  * C/partition/PartitionRuntime.java:255-308) for SoA batches.  Raw partition-key values (64-bit: integers, float

@@ -24,7 +24,7 @@ SYMBOLS = ["sg_open", "sg_push", "sg_advance_time", "sg_pending", "sg_poll", "sg
            "sg_merge_order", "sg_node_open", "sg_node_push", "sg_node_reset", "sg_node_stats_get", "sg_node_keys",
            "sg_node_close", "sg_node_last_error", "sg_node_set_key_dict", "sg_range_open", "sg_range_route",
            "sg_range_stats_get", "sg_range_close", "sg_range_last_error", "sg_node_set_ranges",
-           "sg_node_range_stats_get"]
+           "sg_node_range_stats_get", "sg_set_aggregates"]
 
 I32, I64, U64 = ct.c_int32, ct.c_int64, ct.c_uint64
 
@@ -117,6 +117,16 @@ class sg_range_desc(ct.Structure):
 
 class sg_range_stats(ct.Structure):
     _fields_ = [("rows", I64), ("copies", I64), ("calls", I64), ("hold_ms", ct.c_float), ("expand_ms", ct.c_float)]
+
+
+SG_AGG_ABI_VERSION, SG_MAX_AGG, SG_MAX_GROUP_BY, SG_AGG_MAX_CODE = 1, 8, 4, 64
+
+
+class sg_agg_desc(ct.Structure):
+    _fields_ = [("abi_version", I32), ("n_out", I32), ("kind", I32 * SG_MAX_SELECT), ("arg_type", I32 * SG_MAX_SELECT),
+                ("res_type", I32 * SG_MAX_SELECT), ("n_group", I32), ("group_type", I32 * SG_MAX_GROUP_BY),
+                ("group_off", I32 * SG_MAX_GROUP_BY), ("group_len", I32 * SG_MAX_GROUP_BY), ("code_len", I32),
+                ("code", I64 * SG_AGG_MAX_CODE)]
 
 
 SG_MAX_KMARKS = 24
@@ -213,6 +223,7 @@ def load_library(path: str = LIB_PATH):
         lib.sg_range_last_error.restype = ct.c_char_p
         lib.sg_last_error.argtypes = [P]
         lib.sg_last_error.restype = ct.c_char_p
+        lib.sg_set_aggregates.argtypes = [P, P]
         lib.sg_version.restype = ct.c_char_p
         _lib = lib
     return _lib
@@ -295,7 +306,31 @@ def build_desc(nfa: L.FlatNFA) -> sg_nfa_desc:
     d.n_sched = len(nfa.sched)
     for k, v in enumerate(nfa.sched):
         d.sched_state[k] = v
+    d.has_aggregates = bool(nfa.aggs)    # (a Python attribute, not a field: Node refuses such a query)
     return d
+
+
+def build_agg_desc(nfa: L.FlatNFA):
+    """The query's sg_agg_desc (sg_set_aggregates), or None for a query without aggregates."""
+    if not nfa.aggs:
+        return None
+    a = sg_agg_desc()
+    a.abi_version = SG_AGG_ABI_VERSION
+    a.n_out = len(nfa.out_progs)
+    for k, ag in enumerate(nfa.aggs):
+        if ag is not None:
+            a.kind[k], a.arg_type[k], a.res_type[k] = ag[0], L.TYPE_CODE[ag[1]], L.TYPE_CODE[ag[2]]
+    a.n_group = len(nfa.group_progs)
+    code = []
+    for g, (prog, t) in enumerate(nfa.group_progs):
+        a.group_type[g], a.group_off[g], a.group_len[g] = L.TYPE_CODE[t], len(code), len(prog)
+        code += prog
+    if len(code) > SG_AGG_MAX_CODE:
+        raise L.LoweringError("group by programs too long")
+    a.code_len = len(code)
+    for k, w in enumerate(code):
+        a.code[k] = int(w)
+    return a
 
 
 class Handle:
@@ -321,6 +356,10 @@ class Handle:
 
     def push(self, b: sg_batch):
         self.check(self.lib.sg_push(self.h, ct.byref(b)))
+
+    def set_aggregates(self, a: "sg_agg_desc"):
+        """sg_set_aggregates: once, before the first push."""
+        self.check(self.lib.sg_set_aggregates(self.h, ct.byref(a)))
 
     def advance_time(self, now: int, trigger_index: int):
         """Heartbeat: fire the timers due at `now` (sg_advance_time; one clock-only row)."""
@@ -568,6 +607,9 @@ class Node:
 
     def __init__(self, desc: sg_nfa_desc, n_gpus: int = 1, devices=None, options: sg_options = None,
                  threads: int = 16, chunk_rows: int = 0):
+        if getattr(desc, "has_aggregates", False):
+            from .runtime import SiddhiAppCreationException
+            raise SiddhiAppCreationException("aggregate queries are not supported in the node pipeline (sg_node_*)")
         self._pid = os.getpid()
         self.lib = load_library()
         self.n = ct.c_void_p()
@@ -708,6 +750,9 @@ class GpuEngine:
         if pool:
             opts.pool_partials = opts.pool_events = opts.pool_chain = opts.list_cap = pool
         self.handle = Handle(self.desc, device, opts)
+        self.agg_desc = build_agg_desc(self.nfa)
+        if self.agg_desc is not None:
+            self.handle.set_aggregates(self.agg_desc)
         self.nsel = len(self.nfa.out_progs) or len(self.nfa.select)
         # range-partitioned streams: the device router, unless its limits refuse the query (the runtime then keeps
         # routing on the host)

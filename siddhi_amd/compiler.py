@@ -90,7 +90,19 @@ class Math:
     right: object
 
 
-Expr = Union[Const, Var, Compare, And, Or, Not, IsNull, Math]
+@dataclass
+class AggCall:
+    """An attribute aggregator call in a select expression (SiddhiQL.g4 function_operation; SelectorParser ->
+    AttributeAggregator, C/query/selector/attribute/aggregator/*.java)."""
+    name: str          # count sum avg min max
+    arg: Optional[object]   # None: count()
+
+
+Expr = Union[Const, Var, Compare, And, Or, Not, IsNull, Math, AggCall]
+
+# the aggregators the engines restate, and the names refused by name (the other attribute aggregators of the reference)
+AGGREGATORS = ("count", "sum", "avg", "min", "max")
+_OTHER_AGGREGATORS = ("stddev", "distinctcount", "and", "or", "minforever", "maxforever", "unionset")
 
 
 # ------------------------------------------------------------------------------ state elements
@@ -154,6 +166,7 @@ class Query:
     select: List[OutputAttribute]
     output_stream: str
     having: Optional[object] = None     # QuerySelector havingConditionExecutor (SelectorParser.java:98-100)
+    group_by: List[Var] = field(default_factory=list)   # GroupByKeyGenerator's executors (SelectorParser.java:85-90)
 
 
 @dataclass
@@ -421,12 +434,31 @@ class _Parser:
             select.append(OutputAttribute(e, rename))
             if not self.accept(","):
                 break
+        group_by = []
+        if self._at_words("group", "by"):   # group_by: GROUP BY attribute_reference (',' attribute_reference)*
+            self.i += 2
+            while True:
+                g = self.expr()
+                if not isinstance(g, Var):
+                    raise SiddhiParserException("group by takes attribute references only")
+                group_by.append(g)
+                if not self.accept(","):
+                    break
         having = self.expr() if self.accept("having") else None
+        if self._at_words("order", "by"):
+            raise SiddhiParserException("order by is not supported")
+        for w in ("limit", "offset"):
+            if self._at_words(w):
+                raise SiddhiParserException(f"{w} is not supported")
         self.eat("insert")
         self.eat("into")
         out = self.ident()
         self.accept(";")
-        return Query(name, inp, select, out, having)
+        return Query(name, inp, select, out, having, group_by)
+
+    def _at_words(self, *words) -> bool:
+        """the next tokens spell `words` (clause words that are no keywords of the pattern grammar: plain identifiers)"""
+        return all(self.peek(k).kind in ("id", "kw") and self.peek(k).text.lower() == w for k, w in enumerate(words))
 
     # -- state input
     def state_input(self) -> StateInputStream:
@@ -735,7 +767,23 @@ class _Parser:
             return Const("BOOL", t.text == "true")
         if t.kind == "kw" and t.text == "null":
             raise SiddhiParserException("null literal not supported")
+        if t.kind == "kw" and t.text in ("and", "or") and self.at("(", 1):
+            raise SiddhiParserException(f"aggregator {t.text}() is not supported")
         name = self.ident()
+        if self.at("("):    # function_operation: only the attribute aggregators the engines restate
+            fn = name.lower()
+            if fn in _OTHER_AGGREGATORS:
+                raise SiddhiParserException(f"aggregator {name}() is not supported")
+            if fn not in AGGREGATORS:
+                raise SiddhiParserException(f"function {name}() is not supported")
+            self.eat("(")
+            arg = None if self.at(")") else self.expr()
+            if self.accept(","):
+                raise SiddhiParserException(f"{name}() takes one argument")
+            self.eat(")")
+            if arg is None and fn != "count":
+                raise SiddhiParserException(f"{name}() needs an argument")
+            return AggCall(fn, arg)
         index = None
         if self.at("["):
             self.eat("[")

@@ -10,6 +10,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "agg.h"
 #include "sg_engine.h"
 #include "sg_prim.h"
 
@@ -72,6 +73,19 @@ __global__ void k_having_scatter(int64_t n, const char* __restrict__ src, const 
   for (int w = 0; w < stride / 8; ++w) t[w] = s[w];
 }
 
+// `having` over output records whose aggregate columns the aggregation stage has filled (QuerySelector.processGroupBy
+// runs the having executor after the aggregators, C/query/selector/QuerySelector.java:171-216)
+__global__ void k_having(int64_t n, const char* __restrict__ rec, int stride, const DevDesc* __restrict__ d,
+                         uint32_t* __restrict__ keep) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const char* o = rec + (size_t)i * stride;
+  SelReader hr;
+  hr.vals = (const int64_t*)(o + 32);
+  hr.vnull = *(const uint32_t*)(o + 24);
+  keep[i] = sg_eval(d->code + d->having_off, d->having_len, hr) ? 1u : 0u;
+}
+
 // Engines append base records to h.stage (swapped in for the push); the select pass appends the output
 // records (those passing `having`) to h.out.
 static void run_select(SgHandle& h) {
@@ -80,7 +94,35 @@ static void run_select(SgHandle& h) {
   const int64_t n = h.stage.n;
   const int ostride = 32 + 8 * d.n_out;
   const dim3 grd((unsigned)((n + 255) / 256)), blk(256);
-  if (n > 0 && d.having_len <= 0) {
+  if (n > 0 && h.agg) {
+    // aggregates: k_select leaves every aggregator's argument in its column, the stage turns them into running
+    // values in place, `having` then sees the aggregated columns (a match it drops has updated its aggregators)
+    const bool hav = d.having_len > 0;
+    char* rec = hav ? (char*)h.ws.get("having_rec", (size_t)n * ostride, st)
+                    : h.out.reserve(n, d.n_out, st) + (size_t)h.out.n * ostride;
+    hipLaunchKernelGGL(k_select, grd, blk, 0, st, n, (const char*)h.stage.rec, 32 + 8 * d.n_select, rec, ostride,
+                       h.ddesc, (uint32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    sg_agg_run(h, h.agg, (const char*)h.stage.rec, 32 + 8 * d.n_select, rec, ostride, n);
+    if (!hav) {
+      h.out.n += n;
+    } else {
+      uint32_t* keep = (uint32_t*)h.ws.get("having_keep", 4 * (size_t)(n + 1), st);
+      uint32_t* pos = (uint32_t*)h.ws.get("having_pos", 4 * (size_t)(n + 1), st);
+      HIPCHK(hipMemsetAsync(keep + n, 0, 4, st));
+      hipLaunchKernelGGL(k_having, grd, blk, 0, st, n, (const char*)rec, ostride, h.ddesc, keep);
+      HIPCHK(hipGetLastError());
+      sg_exclusive_scan(h.ws, st, "having_scan_tmp", keep, pos, 0u, (size_t)n + 1, rocprim::plus<uint32_t>());
+      uint32_t kept = sg_read_back(pos + n, st);
+      if (kept) {
+        char* out = h.out.reserve(kept, d.n_out, st);
+        hipLaunchKernelGGL(k_having_scatter, grd, blk, 0, st, n, (const char*)rec, keep, pos, ostride,
+                           out + (size_t)h.out.n * ostride);
+        HIPCHK(hipGetLastError());
+        h.out.n += kept;
+      }
+    }
+  } else if (n > 0 && d.having_len <= 0) {
     char* out = h.out.reserve(n, d.n_out, st);
     hipLaunchKernelGGL(k_select, grd, blk, 0, st, n, (const char*)h.stage.rec, 32 + 8 * d.n_select,
                        out + (size_t)h.out.n * ostride, ostride, h.ddesc, (uint32_t*)nullptr);
@@ -531,6 +573,18 @@ int sg_open(int hip_device, const sg_nfa_desc* nfa, const sg_options* opt, sg_ha
   return SG_OK;
 }
 
+int sg_set_aggregates(sg_handle* hh, const sg_agg_desc* a) {
+  if (!hh || !a) return SG_EINVAL;
+  SgHandle& h = hh->h;
+  return guard(hh, [&] {
+    if (!h.ddesc) throw SgError(SG_EINVAL, "sg_set_aggregates on a handle that did not open");
+    if (h.agg) throw SgError(SG_EINVAL, "sg_set_aggregates: the handle has its aggregates already");
+    if (h.gen != 0) throw SgError(SG_EINVAL, "sg_set_aggregates after the first push, reset or restore");
+    HIPCHK(hipSetDevice(h.device));
+    h.agg = sg_agg_new(h, a);
+  });
+}
+
 int sg_push(sg_handle* hh, const sg_batch* b) {
   if (!hh || !b) return SG_EINVAL;
   SgHandle& h = hh->h;
@@ -718,6 +772,7 @@ int sg_reset(sg_handle* hh) {
     sg_every_absent_reset(&h);
     sg_general_reset(&h);
     sg_once_reset(&h);
+    sg_agg_reset(h, h.agg);
   });
 }
 
@@ -737,6 +792,7 @@ int sg_get_timing(sg_handle* hh, sg_timing* t) {
   SgHandle& h = hh->h;
   return guard(hh, [&] {
     HIPCHK(hipEventSynchronize(h.ev[4]));
+    if (h.n_km) HIPCHK(hipEventSynchronize(h.km[h.n_km - 1][1]));   // (the select pass marks kernels after ev[4])
     float a = 0, b = 0, c = 0, d = 0;
     HIPCHK(hipEventElapsedTime(&a, h.ev[0], h.ev[1]));
     HIPCHK(hipEventElapsedTime(&b, h.ev[1], h.ev[2]));
@@ -774,6 +830,8 @@ int sg_close(sg_handle* hh) {
   sg_every_absent_release(&h);
   sg_general_release(&h);
   sg_once_release(&h);
+  sg_agg_free(h.agg);
+  h.agg = nullptr;
   h.ws.release();
   h.out.release();
   h.stage.release();
@@ -825,6 +883,7 @@ static uint64_t query_fingerprint(const SgHandle& h) {
   for (int k = 0; k < d.n_out; ++k) { mix(d.out_type[k]); mix(d.out_off[k]); mix(d.out_len[k]); }
   mix(d.code_len);
   for (int k = 0; k < d.code_len; ++k) mix(d.code[k]);
+  if (h.agg) x = sg_agg_fingerprint(h.agg, x);   // (a query without aggregates keeps the fingerprint it had)
   return x;
 }
 
@@ -864,6 +923,7 @@ int sg_snapshot(sg_handle* hh, void* buf, size_t cap, size_t* size) {
       case 4: sg_once_snapshot(&h, w); break;
       default: break;
     }
+    if (h.agg) sg_agg_snapshot(h, h.agg, w);   // after the route's own state
     *size = w.b.size();
     if (buf && cap >= w.b.size()) {
       memcpy(buf, w.b.data(), w.b.size());
@@ -901,6 +961,7 @@ int sg_restore(sg_handle* hh, const void* buf, size_t size) {
     sg_every_absent_reset(&h);
     sg_general_reset(&h);
     sg_once_reset(&h);
+    sg_agg_reset(h, h.agg);
     switch (kind) {
       case 1: sg_every_next_restore(&h, r); break;
       case 2: sg_general_restore(&h, r); break;
@@ -908,6 +969,7 @@ int sg_restore(sg_handle* hh, const void* buf, size_t size) {
       case 4: sg_once_restore(&h, r); break;
       default: break;
     }
+    if (h.agg) sg_agg_restore(h, h.agg, r);
     if (r.p != r.e) throw SgError(SG_EINVAL, "trailing bytes in snapshot");
     h.pushes = (int)pushes;
     h.key_bound_seen = kb;

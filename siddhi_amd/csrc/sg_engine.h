@@ -101,6 +101,8 @@ struct BatchView {
   int32_t key_bound;
 };
 
+struct AggStage;   // the selector's aggregation stage (agg.h)
+
 struct SgHandle {
   int device = 0;
   sg_nfa_desc desc;
@@ -123,6 +125,7 @@ struct SgHandle {
   } eg;
   int64_t last_events = 0, last_matches = 0, last_spilled = 0;
   int pushes = 0;
+  AggStage* agg = nullptr;    // set by sg_set_aggregates: run_select aggregates between k_select and `having`
   uint64_t gen = 0;           // state generation: bumped by every push / reset / restore
   std::vector<char> snap_cache;   // blob of the last size query (sg_snapshot), valid while gen == snap_gen
   uint64_t snap_gen = ~0ull;

@@ -157,6 +157,8 @@ def _enc_expr(ctx: QueryContext, e) -> List[int]:
         return [16] + _enc_expr(ctx, e.expr)
     if isinstance(e, C.Math):
         return [17, MATH_CODE[e.op]] + _enc_expr(ctx, e.left) + _enc_expr(ctx, e.right)
+    if isinstance(e, C.AggCall):
+        raise LoweringError(f"aggregate {e.name}() is not supported on the oracle engine (its image has no code for it)")
     raise LoweringError(f"unsupported expression {e}")
 
 
@@ -203,6 +205,36 @@ def oracle_image(ctx: QueryContext) -> List[int]:
     else:
         img += [1] + _enc_having(ctx, q.having)
     return img
+
+
+AGG_KIND = {"count": 1, "sum": 2, "avg": 3, "min": 4, "max": 5}     # SG_AGG_* (include/siddhi_gpu.h)
+MAX_AGG, MAX_GROUP_BY = 8, 4
+
+
+def agg_result_type(name: str, arg_type: Optional[str]) -> str:
+    """getReturnType of the aggregator classes (C/query/selector/attribute/aggregator/): count LONG
+    (CountAttributeAggregator.java:72-74); sum LONG for INT / LONG and DOUBLE for FLOAT / DOUBLE
+    (SumAttributeAggregator.java:84-100); avg DOUBLE (AvgAttributeAggregator.java:78-95); min / max the argument's type
+    (MaxAttributeAggregator.java:85-103).  Other argument types are an OperationNotSupportedException at creation."""
+    if name == "count":
+        return "LONG"
+    if arg_type not in ("INT", "LONG", "FLOAT", "DOUBLE"):
+        raise LoweringError(f"{name} not supported for {arg_type}")
+    if name == "sum":
+        return "LONG" if arg_type in ("INT", "LONG") else "DOUBLE"
+    if name == "avg":
+        return "DOUBLE"
+    return arg_type
+
+
+def _has_agg(e) -> bool:
+    if isinstance(e, C.AggCall):
+        return True
+    if isinstance(e, (C.Math, C.Compare, C.And, C.Or)):
+        return _has_agg(e.left) or _has_agg(e.right)
+    if isinstance(e, (C.Not, C.IsNull)):
+        return _has_agg(e.expr)
+    return False
 
 
 def having_output_index(q, v) -> int:
@@ -346,6 +378,11 @@ class FlatNFA:
     out_types: List[str] = field(default_factory=list)
     having_prog: list = field(default_factory=list)   # postfix over the output columns (VAR word 3 = column)
     sched: List[int] = field(default_factory=list)    # scheduler states in creation order (sg_nfa_desc.sched_state)
+    # attribute aggregators (sg_agg_desc): per output column None or (kind, argument TYPE, result TYPE) -- the column's
+    # out_prog is then the aggregator's argument and its out_type the result type; group_progs: per group-by
+    # attribute (postfix program over the `select` slots, TYPE).  Both empty for a query without aggregates.
+    aggs: list = field(default_factory=list)
+    group_progs: list = field(default_factory=list)
 
 
 def _cmp_domain(lt: str, rt: str, op: str) -> int:
@@ -660,10 +697,39 @@ class _FlatBuilder:
                 return lw + rw + [OP_MATH, MATH_CODE[e.op], TYPE_CODE[t]], t
             raise LoweringError(f"unsupported select expression {e}")
 
+        aggs = []
         for oa in q.select:
-            w, t = sel_prog(oa.expr)
+            e = oa.expr
+            if isinstance(e, C.AggCall):
+                # SelectorParser: the aggregator's argument executor runs per match, the aggregator returns the column
+                if e.arg is not None and _has_agg(e.arg):
+                    raise LoweringError(f"aggregate call nested inside {e.name}() is not supported")
+                w, at = sel_prog(e.arg) if e.arg is not None else ([OP_CONST, TYPE_CODE["INT"], 0], "INT")
+                t = agg_result_type(e.name, at)
+                aggs.append((AGG_KIND[e.name], at, t))
+            else:
+                if _has_agg(e):
+                    raise LoweringError(f"an aggregate call nested inside a larger select expression "
+                                        f"({oa.rename}) is not supported")
+                w, t = sel_prog(e)
+                aggs.append(None)
             out_progs.append(w)
             out_types.append(t)
+        if sum(a is not None for a in aggs) > MAX_AGG:
+            raise LoweringError(f"more than {MAX_AGG} aggregate outputs in one query")
+        if len(q.group_by) > MAX_GROUP_BY:
+            raise LoweringError(f"more than {MAX_GROUP_BY} group by attributes in one query")
+        group_progs = []
+        for g in q.group_by:     # GroupByKeyGenerator: one variable executor per attribute
+            if not isinstance(g, C.Var):
+                raise LoweringError("group by takes attribute references only")
+            if any(a is not None for a in aggs):
+                k, t = base_slot(g)
+                group_progs.append(([OP_VAR, 0, 0, k, TYPE_CODE[t]], t))
+            else:
+                self.resolve(g, -1, True)    # without aggregators the groups change no output: only checked
+        if not any(a is not None for a in aggs):
+            aggs = []
         having_prog = []
         if q.having is not None:
             def hav(e):
@@ -701,6 +767,7 @@ class _FlatBuilder:
                       self.states, receivers, order, ro, uo, start_ids, self.retained, select,
                       column_layout(self.ctx))
         nfa.out_progs, nfa.out_types, nfa.having_prog = out_progs, out_types, having_prog
+        nfa.aggs, nfa.group_progs = (aggs, group_progs) if out_progs else ([], [])
         self.sched_order(root, nfa.sched)
         _classify(nfa, root, self)
         return nfa

@@ -329,15 +329,28 @@ class _QueryRuntime:
             L.lower(self.ctx)
         except L.LoweringError as x:
             raise SiddhiAppCreationException(str(x)) from x
-        self.engine = engine_factory(self.ctx)
+        try:
+            self.engine = engine_factory(self.ctx)
+        except L.LoweringError as x:     # what this engine does not run (aggregates on the oracle)
+            raise SiddhiAppCreationException(str(x)) from x
         self.query_callbacks: List[QueryCallback] = []
 
     def _select_type(self, e):
         if isinstance(e, C.Const):
             return e.type
         if isinstance(e, C.Math):      # ExpressionParser.parseArithmeticOperationResultType (:1413-1431)
+            if L._has_agg(e):
+                raise SiddhiAppCreationException("an aggregate call nested inside a larger select expression is not "
+                                                 "supported")
             try:
                 return L.math_type(self._select_type(e.left), self._select_type(e.right))
+            except L.LoweringError as x:
+                raise SiddhiAppCreationException(str(x)) from x
+        if isinstance(e, C.AggCall):   # the aggregator's getReturnType (lowering.agg_result_type)
+            if e.arg is not None and L._has_agg(e.arg):
+                raise SiddhiAppCreationException(f"aggregate call nested inside {e.name}() is not supported")
+            try:
+                return L.agg_result_type(e.name, None if e.arg is None else self._select_type(e.arg))
             except L.LoweringError as x:
                 raise SiddhiAppCreationException(str(x)) from x
         if not isinstance(e, C.Var):
