@@ -447,6 +447,11 @@ int sg_node_set_ranges(sg_node* nd, const sg_range_desc* d, const int64_t* label
 int sg_node_range_stats_get(const sg_node* nd, sg_range_stats* st);   /* rows in / copies out since open or reset */
 int sg_node_stats_get(const sg_node* nd, sg_node_stats* st);
 int sg_node_keys(const sg_node* nd, int64_t* n_keys);
+/* The device key dictionary of one shard: slots of its table (0 before the shard's first row), keys it holds, probe
+ * launches and table rebuilds (4x each) since the node was opened.  Any out pointer may be NULL.  SG_EINVAL for a shard
+ * outside [0, n_gpus) or while the stream's keys are encoded on the host (and before the first push of a stream). */
+int sg_node_key_dict_stats(const sg_node* nd, int shard, int64_t* cap, int64_t* n_keys, int64_t* probes,
+                           int64_t* rebuilds);
 int sg_node_close(sg_node* nd);
 const char* sg_node_last_error(const sg_node* nd);
 

@@ -24,7 +24,7 @@ SYMBOLS = ["sg_open", "sg_push", "sg_advance_time", "sg_pending", "sg_poll", "sg
            "sg_merge_order", "sg_node_open", "sg_node_push", "sg_node_reset", "sg_node_stats_get", "sg_node_keys",
            "sg_node_close", "sg_node_last_error", "sg_node_set_key_dict", "sg_range_open", "sg_range_route",
            "sg_range_stats_get", "sg_range_close", "sg_range_last_error", "sg_node_set_ranges",
-           "sg_node_range_stats_get", "sg_set_aggregates"]
+           "sg_node_range_stats_get", "sg_set_aggregates", "sg_node_key_dict_stats"]
 
 I32, I64, U64 = ct.c_int32, ct.c_int64, ct.c_uint64
 
@@ -209,6 +209,7 @@ def load_library(path: str = LIB_PATH):
         lib.sg_node_reset.argtypes = [P]
         lib.sg_node_stats_get.argtypes = [P, P]
         lib.sg_node_keys.argtypes = [P, ct.POINTER(I64)]
+        lib.sg_node_key_dict_stats.argtypes = [P, ct.c_int] + [ct.POINTER(I64)] * 4
         lib.sg_node_close.argtypes = [P]
         lib.sg_node_set_key_dict.argtypes = [P, ct.c_int]
         lib.sg_node_set_ranges.argtypes = [P, P, P]
@@ -643,6 +644,15 @@ class Node:
         n = I64()
         self.check(self.lib.sg_node_keys(self.n, ct.byref(n)))
         return n.value
+
+    def key_dict_stats(self, shard: int = 0) -> dict:
+        """sg_node_key_dict_stats: the shard's device dictionary -- table slots, keys held, probe launches and
+        rebuilds since open.  SgError(SG_EINVAL) for a bad shard or while keys are encoded on the host."""
+        v = [I64() for _ in range(4)]
+        rc = self.lib.sg_node_key_dict_stats(self.n, int(shard), *[ct.byref(x) for x in v])
+        if rc != 0:
+            raise SgError(rc, "sg_node_key_dict_stats: bad shard, or no device dictionary in use")
+        return dict(zip(("cap", "n_keys", "probes", "rebuilds"), (x.value for x in v)))
 
     def reset(self):
         self.check(self.lib.sg_node_reset(self.n))

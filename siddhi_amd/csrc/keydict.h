@@ -13,6 +13,12 @@
 //           first-seen order of the whole stream, chunk after chunk;
 //   fill    pending rows look their key up again.
 // A table that would pass half full is rebuilt 4x larger and the chunk re-probed (pending claims dropped).
+//
+// Fill invariant: claims are admitted while claims + n_keys < cap / 2 and every probing thread may overshoot that by
+// one, so the probe grid is bounded by the capacity (at most cap / 4 threads; 1024 blocks from 4M slots upward) and
+// the table stays under 3/4 full: no probe loop can run out of empty slots.  kd_resolve checks it before each launch.
+// SG_DEBUG_KD_CAP (a test hook, read when the first table is allocated) sets the initial capacity: a power of two
+// between 1024 and the production 4M slots; any other value fails the resolve with SG_EINVAL.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

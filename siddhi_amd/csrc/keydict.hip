@@ -1,6 +1,7 @@
 // Device key dictionary (see keydict.h).
 #include "keydict.h"
 
+#include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -21,6 +22,7 @@ const int32_t KD_UNUSED = (int32_t)0x80000000u;
 const int KD_BLOCK = 256;
 const int KD_MAX_BLOCKS = 1024;              // at most 256K probing threads: claims overshoot the limit by <= that
 const int64_t KD_MIN_CAP = (int64_t)1 << 22;  // 4M slots (48 MB): a million keys without a rebuild
+const int64_t KD_DEBUG_MIN_CAP = 1024;        // smallest initial table SG_DEBUG_KD_CAP may ask for (one probe block)
 
 struct KdView {
   int64_t* keys;
@@ -193,6 +195,41 @@ unsigned grid_for(int64_t n) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(KD_MAX_BLOCKS, (n + KD_BLOCK - 1) / KD_BLOCK));
 }
 
+// The table never fills.  kd_room admits a claim only while claims + n_keys < cap / 2, and a thread that passed the
+// check makes at most one claim before it checks again: after the last check that passes (claims + n_keys <= cap / 2
+// - 1) only the threads then between their check and their count can still claim, one each, so a probe leaves fewer
+// than cap / 2 + (probing threads) occupied slots.  The probe grid is bounded by the capacity -- at most cap / 4
+// threads -- which keeps that under 3/4 cap: every probe loop of k_kd_probe and k_kd_fill meets an empty slot or its
+// own key (k_kd_rehash moves fewer than cap / 8 keys into an empty table).  1024 blocks from 4M slots upward; a
+// smaller table only exists under SG_DEBUG_KD_CAP.  probe_grid checks the inequality before every probe launch.
+int64_t probe_blocks(int64_t cap) {
+  return std::max<int64_t>(1, std::min<int64_t>(KD_MAX_BLOCKS, cap / (4 * KD_BLOCK)));
+}
+
+unsigned probe_grid(const KeyDict& t, int64_t n) {
+  const int64_t blocks = std::min<int64_t>(probe_blocks(t.cap), grid_for(n));
+  if (t.cap < KD_DEBUG_MIN_CAP || (t.cap & (t.cap - 1)) != 0 || t.cap / 2 + blocks * KD_BLOCK >= t.cap ||
+      t.list_cap < t.cap / 2 + blocks * KD_BLOCK)
+    throw SgError(SG_EINVAL, "keydict: internal: the probe grid could fill the table (capacity " +
+                                 std::to_string(t.cap) + ", " + std::to_string(blocks) + " blocks)");
+  return (unsigned)blocks;
+}
+
+int64_t lists_for(int64_t cap) { return cap / 2 + probe_blocks(cap) * KD_BLOCK; }
+
+// the capacity of a new dictionary's first table: KD_MIN_CAP, or SG_DEBUG_KD_CAP (a test hook: rebuilds and probe
+// chains at test sizes) -- a power of two in [1024, KD_MIN_CAP], anything else is refused
+int64_t initial_cap() {
+  const char* e = getenv("SG_DEBUG_KD_CAP");
+  if (!e) return KD_MIN_CAP;
+  char* end = nullptr;
+  const long long v = strtoll(e, &end, 10);
+  if (end == e || *end != 0 || v < KD_DEBUG_MIN_CAP || v > KD_MIN_CAP || (v & (v - 1)) != 0)
+    throw SgError(SG_EINVAL, std::string("keydict: SG_DEBUG_KD_CAP must be a power of two between 1024 and ") +
+                                 std::to_string(KD_MIN_CAP) + ", not '" + e + "'");
+  return (int64_t)v;
+}
+
 void alloc_table(KeyDict& t, int64_t cap, hipStream_t st) {
   KDCHK(hipMalloc((void**)&t.keys, sizeof(int64_t) * (cap + 1)));
   KDCHK(hipMalloc((void**)&t.vals, sizeof(int32_t) * (cap + 1)));
@@ -236,7 +273,7 @@ void rebuild(KeyDict& t, int64_t cap, hipStream_t st) {
   t.vals = nt.vals;
   t.first = nt.first;
   t.cap = cap;
-  ensure_lists(t, cap / 2 + (int64_t)KD_MAX_BLOCKS * KD_BLOCK, st);
+  ensure_lists(t, lists_for(cap), st);
   ++t.rebuilds;
 }
 
@@ -251,18 +288,19 @@ int64_t kd_resolve(KeyDict& t, const int64_t* raw, const int32_t* stream, int64_
     KDCHK(hipHostMalloc((void**)&t.hctr, 2 * sizeof(uint32_t), hipHostMallocDefault));
   }
   if (!t.keys || t.clear) {
-    if (!t.keys) alloc_table(t, KD_MIN_CAP, st);
+    if (!t.keys) alloc_table(t, initial_cap(), st);
     else hipLaunchKernelGGL(k_kd_clear, dim3(grid_for(t.cap + 1)), dim3(KD_BLOCK), 0, st, t.keys, t.vals, t.first,
                             t.cap);
     KDCHK(hipGetLastError());
-    ensure_lists(t, t.cap / 2 + (int64_t)KD_MAX_BLOCKS * KD_BLOCK, st);
+    ensure_lists(t, lists_for(t.cap), st);
     t.n_keys = 0;
     t.clear = false;
   }
   int64_t m = 0;
   while (true) {
     KDCHK(hipMemsetAsync(t.ctr, 0, 2 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_kd_probe, dim3(grid_for(n)), dim3(KD_BLOCK), 0, st, view(t), raw, stream, n, key, t.ctr);
+    const unsigned pg = probe_grid(t, n);   // (throws rather than launch a grid that could fill the table)
+    hipLaunchKernelGGL(k_kd_probe, dim3(pg), dim3(KD_BLOCK), 0, st, view(t), raw, stream, n, key, t.ctr);
     KDCHK(hipGetLastError());
     KDCHK(hipMemcpyAsync(t.hctr, t.ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KDCHK(hipStreamSynchronize(st));

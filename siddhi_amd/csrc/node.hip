@@ -1036,10 +1036,9 @@ void route_chunk(Run& r, int64_t j) {
   nd.pool->parallel_for(T, [&](int t) {
     int64_t a, e;
     slice(t, a, e);
-    sgr::lookup_slice(rt->dict, raw + a, e - a, dense + a, miss[t]);
-    if (stream)   // clock-only rows (stream -1) carry no key: every shard sees them
-      for (int64_t i = a; i < e; ++i)
-        if (stream[i] < 0) dense[i] = -1;
+    // clock-only rows (stream -1) carry no key (their raw value is not looked up: it must not get an id): -1, and
+    // every shard sees them
+    sgr::lookup_slice(rt->dict, raw + a, e - a, dense + a, miss[t], stream ? stream + a : nullptr);
     if (G > 1) {
       const int32_t* so = rt->shard_of.data();
       int64_t* c = cnt[t].data();
@@ -2494,6 +2493,7 @@ int sg_node_reset(sg_node* nd) {
     nd->local_rows[s] = 0;
     kd_reset(nd->kd[s]);
     nd->l2g[s].clear();
+    nd->x[s].l2g_n = 0;   // (the device copy is uploaded again from entry 0: the new stream's ids, not the old one's)
   }
   nd->g_keys = 0;
   nd->ddict = -1;
@@ -2521,6 +2521,17 @@ int sg_node_keys(const sg_node* nd, int64_t* n_keys) {
     return SG_OK;
   }
   return sg_router_keys(nd->router, n_keys, -1, nullptr);
+}
+
+int sg_node_key_dict_stats(const sg_node* nd, int shard, int64_t* cap, int64_t* n_keys, int64_t* probes,
+                           int64_t* rebuilds) {
+  if (!nd || shard < 0 || shard >= nd->G || nd->ddict != 1) return SG_EINVAL;   // (ddict 0: keys are on the host)
+  const KeyDict& t = nd->kd[shard];
+  if (cap) *cap = t.cap;
+  if (n_keys) *n_keys = t.n_keys;
+  if (probes) *probes = t.probes;
+  if (rebuilds) *rebuilds = t.rebuilds;
+  return SG_OK;
 }
 
 int sg_node_set_key_dict(sg_node* nd, int mode) {

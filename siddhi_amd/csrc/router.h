@@ -88,9 +88,15 @@ struct SliceMiss {
   bool any = false;
 };
 // out[i] = dictionary id of raw[i], or -(slice-local number + 2) for a key the dictionary does not hold yet
-inline void lookup_slice(const KeyMap& dict, const int64_t* raw, int64_t n, int32_t* out, SliceMiss& ms) {
+// (rows whose `stream` entry is < 0 are clock-only: they carry no key, get -1 and add nothing to the dictionary)
+inline void lookup_slice(const KeyMap& dict, const int64_t* raw, int64_t n, int32_t* out, SliceMiss& ms,
+                         const int32_t* stream = nullptr) {
   constexpr int G = 16;   // probes of the next 16 rows in flight
   for (int64_t i = 0; i < n; ++i) {
+    if (stream && stream[i] < 0) {
+      out[i] = -1;
+      continue;
+    }
     if (i + G < n) dict.prefetch(raw[i + G]);
     const int64_t k = raw[i];
     int32_t id = dict.find(k);
