@@ -1,7 +1,8 @@
 // gwalk.h -- the closed form's group walker: `every A[l] -> B[l' and B.x OP A.x] within T` when the partition has
 // many keys with few rows each (C5: 1M keys, ~500 rows per key per 500M-row push, ~10 rows per `within` window).
 // Kernels first, then the host side (gw_plan, run_group_walk); run_every_next (engine_impl.h) tries run_group_walk
-// after the partition's group passes (keypart.h part1_wide).
+// after the partition's group passes (keypart.h part1_wide).  The delivery side -- the trigger-word format, the tile
+// counts and the projection kernel -- is gw_proj.h.
 //
 // Semantics are those of the tiled walker (walk.h Walker::step, itself StreamPreStateProcessor.isExpired /
 // processAndReturn, C/query/input/stream/state/StreamPreStateProcessor.java:102-113,292-337, and
@@ -39,6 +40,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "gw_proj.h"
 #include "keypart.h"
 #include "sg_engine.h"
 #include "sg_prim.h"
@@ -74,17 +76,6 @@ struct GwArgs {
   uint32_t* match_n;          // matches of the push (the projection's output size)
 };
 static const uint32_t GW_ORDER = 1, GW_OVERFLOW = 2, GW_INTERNAL = 4, GW_CARRY_FULL = 8;
-
-// Trigger word: unit (32) | matches (24) | epoch (8).  The buffer is not cleared per push: a word counts only when
-// its epoch is the push's (run_group_walk hands the epochs out and clears what could hold anything else).
-static const uint32_t GW_MATCH_MAX = (1u << 24) - 1;
-__device__ __forceinline__ uint64_t gw_trig_word(uint64_t unit, uint32_t m, uint32_t epoch) {
-  return unit | ((uint64_t)m << 32) | ((uint64_t)epoch << 56);
-}
-// matches of a trigger word under `epoch` (0: the row triggered nothing in this push)
-__device__ __forceinline__ uint32_t gw_trig_matches(uint64_t w, uint32_t epoch) {
-  return (uint32_t)(w >> 56) == epoch ? (uint32_t)(w >> 32) & GW_MATCH_MAX : 0u;
-}
 
 // per-key rows of every group (LDS counters over the group's in-group keys, read 16 bytes per lane between a scalar
 // head and tail) -> each key's first row in the group domain: the group's keys lie one after the other from the
@@ -462,109 +453,6 @@ __global__ void __launch_bounds__(256) k_gw_redo(GwArgs a, uint32_t* __restrict_
   W.carry(a, o);
 }
 
-// Output records in delivery order: one thread per batch row (trigger order = arrival order).  A trigger's matches
-// are read from its header in the match area (one 16-byte header + 8 bytes per match, contiguous) and assembled in
-// LDS at their position inside the block's output range, which is then stored contiguously (whole lines, 16-byte
-// stores by consecutive threads); a block whose rows deliver more than GW_PROJ_S records does it in rounds.
-struct GwSel {
-  int32_t n_select, stride, multi, b_slot, pzero, vfloat;
-  uint32_t nmask;      // null-mask bits of the record: the columns of code 4
-  uint32_t pad;
-  uint64_t codes[2];   // 4 bits per select column: 0 e1 payload, 1 e1 value, 2 e2 value, 3 e2 payload, 4 null
-};
-static_assert(SG_MAX_SELECT <= 32, "GwSel packs 32 select codes");
-static const int GW_PROJ_S = 256;   // records staged per round
-static const int GW_TILE = 256;     // rows per projection tile (one per thread)
-
-// matches per 256-row tile of trigger words, eight tiles per workgroup (the projection's tile bases come from a scan
-// over these)
-static __global__ void __launch_bounds__(256) k_gtile_count(int64_t n, const uint64_t* __restrict__ trig, uint32_t epoch,
-                                                            uint32_t* __restrict__ tcount, int64_t ntile) {
-  __shared__ uint32_t red[8][4];
-  const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const int64_t r = ((int64_t)blockIdx.x * 8 + s) * GW_TILE + t;
-    uint32_t c = r < n ? gw_trig_matches(__builtin_nontemporal_load(trig + r), epoch) : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
-    if (lane == 0) red[s][w] = c;
-  }
-  __syncthreads();
-  if (t < 8) {
-    const int64_t tile = (int64_t)blockIdx.x * 8 + t;
-    if (tile < ntile) tcount[tile] = red[t][0] + red[t][1] + red[t][2] + red[t][3];
-  }
-}
-
-// Output records: one workgroup per 256-row tile (one row per thread: every trigger's header read is in flight at
-// once), its first output slot from the scanned tile counts and each row's from a block scan; the tile's records are
-// assembled in LDS in slot order and stored contiguously (GW_PROJ_S records per round).
-static __global__ void __launch_bounds__(256) k_gscan_project(int64_t n, int64_t t0, uint64_t base_index,
-                                                              const uint64_t* __restrict__ index,
-                                                              const uint64_t* __restrict__ trig, uint32_t epoch,
-                                                              const uint64_t* __restrict__ area, GwSel sel,
-                                                              int64_t out_base, char* __restrict__ out,
-                                                              const uint32_t* __restrict__ tbase) {
-  extern __shared__ __attribute__((aligned(16))) char stage[];
-  __shared__ uint32_t wsum[4];
-  const uint32_t t = threadIdx.x;
-  const int64_t b = (int64_t)blockIdx.x * GW_TILE + t;
-  const uint64_t tw = b < n ? __builtin_nontemporal_load(trig + b) : 0ull;
-  const uint32_t m = gw_trig_matches(tw, epoch);
-  const uint64_t u = (uint32_t)tw;
-  uint64_t h0 = 0, h1 = 0, tg = 0;
-  if (m) {
-    h0 = area[u];
-    h1 = area[u + 1];
-    tg = index ? index[b] : base_index + (uint64_t)b;
-  }
-  const uint32_t excl = block_excl_scan256(m, wsum);
-  const uint32_t pre = tbase[blockIdx.x];
-  const uint32_t o_lo = pre, o_hi = pre + (wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-  const uint32_t o = pre + excl;
-  auto wid = [&](uint32_t bits, bool zero) { return zero ? (int64_t)bits : (int64_t)(int32_t)bits; };
-  // (the select codes and the null mask come packed in registers: nothing is read from the arguments per match)
-  const uint64_t cw0 = sel.codes[0], cw1 = sel.codes[1];
-  const int nsel = sel.n_select;
-  const int64_t nmask = (int64_t)sel.nmask;
-  const int64_t ts = t0 + (int64_t)(int32_t)(uint32_t)h0;
-  const uint32_t key = (uint32_t)(h0 >> 32);
-  const int64_t v2 = wid((uint32_t)h1, sel.vfloat), p2 = wid((uint32_t)(h1 >> 32), sel.pzero);
-  typedef uint32_t U4 __attribute__((ext_vector_type(4)));
-  for (uint32_t sub = o_lo; sub < o_hi; sub += GW_PROJ_S) {
-    const uint32_t se = (o_hi - sub < (uint32_t)GW_PROJ_S) ? o_hi : sub + GW_PROJ_S;
-    if (m && o < se && o + m > sub) {
-      const uint32_t qa = o < sub ? sub - o : 0u, qe = (o + m > se) ? se - o : m;
-      for (uint32_t q = qa; q < qe; ++q) {
-        const uint64_t e = area[u + 2 + q];
-        const int64_t v1 = wid((uint32_t)e, sel.vfloat), p1 = wid((uint32_t)(e >> 32), sel.pzero);
-        int64_t* r = (int64_t*)(stage + (size_t)(o + q - sub) * sel.stride);
-        r[0] = (int64_t)tg;
-        r[1] = ts;
-        r[2] = (int64_t)((uint64_t)key | ((uint64_t)((1u << 24) | (sel.multi ? (uint32_t)sel.b_slot : (0x800000u | q))) << 32));
-        r[3] = nmask;
-        for (int c = 0; c < nsel; ++c) {
-          const uint32_t code = (uint32_t)((c < 16 ? cw0 >> (4 * c) : cw1 >> (4 * (c - 16))) & 15u);
-          r[4 + c] = code == 0 ? p1 : code == 1 ? v1 : code == 2 ? v2 : code == 3 ? p2 : 0;
-        }
-      }
-    }
-    __syncthreads();
-    const size_t bytes = (size_t)(se - sub) * sel.stride;
-    char* dst = out + (size_t)(out_base + sub) * sel.stride;
-    if ((((uintptr_t)dst) & 15) == 0) {
-      // (an odd select count makes the stride 8 mod 16: an odd number of records ends on a half word, which a 16-byte
-      // store would carry 8 bytes into the next tile's first record -- another workgroup's, or past the buffer)
-      for (size_t x = (size_t)t * 16; x + 16 <= bytes; x += 256 * 16) *(U4*)(dst + x) = *(const U4*)(stage + x);
-      if ((bytes & 8) && t == 255) *(uint64_t*)(dst + bytes - 8) = *(const uint64_t*)(stage + bytes - 8);
-    } else {
-      for (size_t x = (size_t)t * 8; x < bytes; x += 256 * 8) *(uint64_t*)(dst + x) = *(const uint64_t*)(stage + x);
-    }
-    __syncthreads();
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Host side of the group walker: whether a query and a push can take it (gw_plan), and one push through it
 // (run_group_walk).
@@ -665,26 +553,22 @@ static void gw_project(SgHandle* h, const BatchView& bv, int64_t n, const GwArgs
   const sg_nfa_desc& d = h->desc;
   hipStream_t st = h->stream;
   char* out = h->out.reserve(total, d.n_select, st);
-  const int64_t ntile = (n + GW_TILE - 1) / GW_TILE;
+  const int rpt = gw_proj_rpt();   // rows per projection thread: a tile is 256 times that
+  const uint32_t lg_tile = gw_proj_lg_tile(rpt);
+  const int64_t tile = (int64_t)1 << lg_tile;
+  const int64_t ntile = (n + tile - 1) / tile;
   uint32_t* tcount = (uint32_t*)h->ws.get("gw_tcount", sizeof(uint32_t) * ((size_t)ntile + 1), st);
   uint32_t* tbase = (uint32_t*)h->ws.get("gw_tbase", sizeof(uint32_t) * ((size_t)ntile + 1), st);
   h->kbeg("gw_tiles");
   HIPCHK(hipMemsetAsync(tcount + ntile, 0, sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_gtile_count, dim3((unsigned)((ntile + 7) / 8)), dim3(256), 0, st, n, (const uint64_t*)ga.trig, ga.epoch,
-                     tcount, ntile);
-  HIPCHK(hipGetLastError());
+  launch_gtile_count(n, (const uint64_t*)ga.trig, ga.epoch, tcount, ntile, lg_tile, st);
   sg_exclusive_scan(h->ws, st, "gw_tscan_tmp", tcount, tbase, (uint32_t)0, (size_t)ntile + 1, rocprim::plus<uint32_t>());
   h->kend();
   uint32_t tsum = 0;
   HIPCHK(hipMemcpyAsync(&tsum, tbase + ntile, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   h->kbeg("gw_project");
-  const size_t plds = (size_t)GW_PROJ_S * sel.stride;
-  if (plds > 65536)
-    HIPCHK(hipFuncSetAttribute((const void*)k_gscan_project, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
-  hipLaunchKernelGGL(k_gscan_project, dim3((unsigned)ntile), dim3(256), plds, st, n, ga.t0, bv.base_index, bv.index,
-                     (const uint64_t*)ga.trig, ga.epoch, (const uint64_t*)ga.area, sel, (int64_t)h->out.n, out,
-                     (const uint32_t*)tbase);
-  HIPCHK(hipGetLastError());
+  launch_gscan_project(rpt, n, ga.t0, bv.base_index, bv.index, (const uint64_t*)ga.trig, ga.epoch,
+                       (const uint64_t*)ga.area, sel, ntile, (int64_t)h->out.n, out, (const uint32_t*)tbase, st);
   h->kend();
   HIPCHK(hipStreamSynchronize(st));
   if (tsum != total) throw SgError(SG_EINVAL, "internal: group walker match count mismatch");
@@ -745,7 +629,10 @@ static int run_group_walk(SgHandle* h, const BatchView& bv, int64_t n, int64_t n
   h->gw_epoch = wrap ? 1u : h->gw_epoch + 1;
   ga.epoch = h->gw_epoch;
   ga.trig = gw_tagged_words(h, h->gw_trig, "gw_trig", (size_t)std::max<int64_t>(n, 1), wrap, st);
-  ga.area = (uint64_t*)h->ws.get("gw_area", sizeof(uint64_t) * 3 * (size_t)std::max<int64_t>(nt, 1), st);
+  // (a key's rows bound its region with three units to spare -- its first row triggers nothing -- so the projection's
+  // read of two entries behind every header stays inside the region; the pad keeps that true of the last key by
+  // construction, not by that argument)
+  ga.area = (uint64_t*)h->ws.get("gw_area", sizeof(uint64_t) * (3 * (size_t)std::max<int64_t>(nt, 1) + GW_AREA_PAD), st);
   uint32_t* gflags = (uint32_t*)h->ws.get("gw_flags", sizeof(uint32_t) * 4, st);
   ga.flags = gflags;
   ga.cv_n = gflags + 1;
